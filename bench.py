@@ -34,6 +34,8 @@ Rank 0 prints ONE JSON line.  Extra objects:
   stagei             Stage-I on 12 frames / 53 markers / 10 betas: GPU seconds (dense and arrow-structured solver), iterations, and
                      the NumPy oracle's seconds + differences on the same problem
 The reference / CPU / Stage-I legs run at N = 1 only.
+`--dump-outputs DIR`: rank 0 also writes the arrays the headline's last timed step returned as DIR/<name>.npy (`dump_outputs`); the
+inputs are seeded, so two builds of the project can be compared output for output.
 """
 from __future__ import annotations
 
@@ -52,6 +54,7 @@ F64_VALU_PEAK_TFLOPS = 78.6    # MI355X vector FP64 (AMD spec sheet; half the 15
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
 
 
+DUMP_LIMIT = 64 << 20   # bytes written by --dump-outputs at most
 LINE_LIMIT = 3600   # bytes (the driver keeps the last 4-8 KB of stdout; round 6's first line came to 3968): the driver keeps the tail of stdout; the round-5 line (20 KB) was cut and could not be parsed
 
 
@@ -199,6 +202,24 @@ def write_detail(full):
     return wrote
 
 
+def dump_outputs(d, arrays, seed=0):
+    """--dump-outputs: every array as d/<name>.npy in float64 (the int32 iteration counts and status codes are exact in it), so that
+    two builds can be compared output for output.  All arrays share their leading axis (frames); when together they exceed
+    DUMP_LIMIT, the same fixed, seeded sample of those rows is kept of each, and the row indices are written beside them as rows.npy."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    assert all(len(a) == n for a in arrays.values()), {k: a.shape for k, a in arrays.items()}
+    row_bytes = sum(a[:1].nbytes for a in arrays.values())
+    if n * row_bytes > DUMP_LIMIT:
+        keep = (DUMP_LIMIT - (1 << 20)) // (row_bytes + 8)      # 1 MB for the .npy headers; 8 bytes a row for rows.npy
+        rows = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays['rows'] = rows.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + '.npy'), a)
+
+
 def solver_flops(K, Nv, n1, n2, NP, npose, nobs_mean, iters, fevals):
     """Algorithmic FLOPs of the solve (SURVEY.md 8(d) / DESIGN.md 5): forward 2*3Nv*9(K-1) + 2*Nv*K*12 per residual
     evaluation; per Jacobian 3Nv*n*30 + normal equations 2*m*n^2/2 + factorisation n^3/3, m = 3*nobs + (npose+1) + NP."""
@@ -306,7 +327,12 @@ def main():
     ap.add_argument('--lbs-frames', type=int, default=4000)   # the whole solved sequence: that is what a mesh export writes
     ap.add_argument('--pmc-file', default=os.path.join(ROOT, 'profiles', 'r06_pmc.json'),
                     help='HBM traffic from rocprofv3 PMC passes (tools/r06_collect.sh); used only if its source hash is the loaded library\'s')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the arrays the last timed step returned as DIR/<name>.npy (float64, '
+                         f'<= {DUMP_LIMIT >> 20} MB in all: above that a fixed, seeded sample of frames); rank 0 only')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU, rendezvous on 127.0.0.1)
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -374,6 +400,9 @@ def main():
     sm = job['sm']
     F, M = job['vis'].shape
     reports = {sd: [] for sd in seeds}
+    # the headline: the fixed many-sequence job (strong_many) or the timed steps over the seeds below
+    headline_is_strong = (args.scaling == 'strong' or (args.scaling == 'auto' and world > 1)) and args.mode == 'chunked' and not args.no_strong
+    strong_outputs = []     # the headline job's results of its last timed pass on this rank (--dump-outputs)
 
     def barrier():
         if dist is not None:
@@ -406,9 +435,10 @@ def main():
         share = shares[rank]
         stream = torch.cuda.current_stream().cuda_stream
 
-        def solve(idx, reps=1, warm=1, sync=None):
+        def solve(idx, reps=1, warm=1, sync=None, keep=None):
             """`warm` untimed passes over the share (>= 1: allocations inside the library), then `reps` timed ones (a pass = one step of the
-            N > 1 headline); sync(): the ranks' barrier in front of the timed passes.  Returns seconds PER PASS and frames per pass."""
+            N > 1 headline); sync(): the ranks' barrier in front of the timed passes; keep: a list that receives every sequence's results
+            of the last pass.  Returns seconds PER PASS and frames per pass."""
             copies = [workload.DeviceSequence(workload.make_capture(job, solver, 5000 + i), solver, dev) for i in idx]
             per_seq_chunks = max(8, 256 // max(len(copies), 1))      # keep every CU carrying a chain when a rank has few sequences
             for _ in range(max(1, warm)):
@@ -421,6 +451,8 @@ def main():
                 workload.solve_many_chunked(copies, stream, num_chunks=per_seq_chunks)
             torch.cuda.synchronize()
             dt = (time.perf_counter() - t0) / max(1, reps)
+            if keep is not None:
+                keep[:] = [c.results() for c in copies]
             return dt, sum(int((c.results()['status'] != 1).sum()) for c in copies)
 
         t_one, n_one = None, 0
@@ -434,7 +466,7 @@ def main():
         # without a share still meets the barriers); on one GPU the leg is an extra of the default line: one warm-up, one pass
         reps, warm = (args.steps, args.warmup) if headline_is_strong else (1, 1)
         if n_local:
-            t_here, n_here = solve(share, reps=reps, warm=warm, sync=barrier)
+            t_here, n_here = solve(share, reps=reps, warm=warm, sync=barrier, keep=strong_outputs if headline_is_strong else None)
         else:
             barrier()
         barrier()
@@ -562,7 +594,6 @@ def main():
 
     # ---- fixed jobs at this N (all ranks take part)
     strong = None
-    headline_is_strong = (args.scaling == 'strong' or (args.scaling == 'auto' and world > 1)) and args.mode == 'chunked' and not args.no_strong
     if not args.no_strong and args.mode == 'chunked':
         strong = {}
         try:
@@ -611,6 +642,12 @@ def main():
             if 'one_gpu_same_job' in sj:   # the same job on ONE GPU of this box (rank 0 alone, before the sharded run): what `value` is to be divided by
                 result['one_gpu_same_job'] = sj['one_gpu_same_job']
                 result['speedup_vs_one_gpu_same_job'] = sj['one_gpu_same_job']['speedup']
+
+    if args.dump_outputs and rank == 0:
+        # what the headline's last timed step returned: the sequence of the last step, or this rank's share of the fixed job (its
+        # sequences one after the other)
+        outs = strong_outputs if result['scaling'] == 'strong' else [res[seeds[(args.steps - 1) % len(seeds)]]]
+        dump_outputs(args.dump_outputs, {k: np.concatenate([o[k] for o in outs]) for k in outs[0]})
 
     if rank == 0:
         nobs_mean = float(job['vis'].sum(1).mean())

@@ -458,6 +458,36 @@ def test_bench_launches_its_own_ranks(gpu_lib):
 
 
 @pytest.mark.gpu
+def test_bench_dumps_what_its_last_timed_step_computed(gpu_lib, tmp_path):
+    """`bench.py --dump-outputs DIR`: the outputs of the LAST timed step (with --seeds 1000,123 and --steps 2: the seed-123 sequence)
+    as float64 .npy files, one row a frame; the simulated markers fit that sequence's observations, not those of seed 1000."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from moshpp_amd import workload
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--frames', '600',
+                        '--seeds', '1000,123', '--no-cpu', '--no-stagei', '--no-sequential', '--no-strong', '--no-config3', '--lbs-frames', '200',
+                        '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=900, cwd=root)
+    assert p.returncode == 0, p.stderr[-3000:]
+    res = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][0])
+    assert res['steps'] == 2 and res['ms_per_step'] > 0
+    got = {f.name[:-4]: np.load(f) for f in tmp_path.iterdir()}
+    assert set(got) == {'pose', 'fullpose', 'trans', 'markers_sim', 'errs', 'iters', 'status'}
+    assert all(a.dtype == np.float64 and len(a) == 600 for a in got.values())
+    solved = got['status'] != 1
+    assert solved.sum() > 590 and np.isfinite(got['fullpose'][solved]).all()
+
+    def rmse(seed):
+        job = workload.make_job('smplh', n_frames=600, n_markers=53, seed=seed)
+        vis = job['vis'][solved]
+        return float(np.sqrt((((got['markers_sim'][solved] - job['obs'][solved]) ** 2).sum(-1) * vis).sum() / vis.sum()))
+    fit = rmse(123)
+    assert fit < 5e-3 and rmse(1000) > 10 * fit
+
+
+@pytest.mark.gpu
 def test_chunked_solve_is_exact_under_gpu_contention(gpu_lib):
     """The chunk protocol's waits are bounded spins between workgroups that are normally all resident (one per CU).  Here another
     stream keeps the GPU busy with large matrix products while the 4000-frame sequence is solved chunk-parallel, so that chunk

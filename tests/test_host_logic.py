@@ -403,7 +403,7 @@ def test_the_default_chain_mode_is_chunked_only_for_long_body_only_solves():
 
 
 def test_bench_takes_counter_numbers_only_from_the_build_it_runs(tmp_path):
-    """bench.py --pmc-file: the committed PMC summary (profiles/r05_pmc.json, tools/r05_collect.sh) carries the source hash of the
+    """bench.py --pmc-file: the committed PMC summary (profiles/r06_pmc.json, bench.py's default, tools/r06_collect.sh) carries the source hash of the
     library it was collected on; a file of another build -- or none -- gives (None, why), never numbers.  The committed file should be
     the one of THIS tree's native sources (then the driver's bench line prints `traffic`, not null); if it is not, the test says so and skips."""
     import json
@@ -418,9 +418,9 @@ def test_bench_takes_counter_numbers_only_from_the_build_it_runs(tmp_path):
     assert d is None and 'not used' in note
     d, note = bench.load_pmc(str(tmp_path / 'missing.json'), 'abc')
     assert d is None and 'no PMC file' in note
-    committed = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'r05_pmc.json')
+    committed = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'r06_pmc.json')
     d, note = bench.load_pmc(committed, build.source_hash())
     if d is None:   # (native sources edited since the last collection: stale evidence, not a broken product)
         import pytest
-        pytest.skip(f'{note} -- re-run tools/r05_collect.sh on a GPU box and copy gpurun_out/r05/r05_pmc.json to profiles/')
+        pytest.skip(f'{note} -- re-run tools/r06_collect.sh on a GPU box and copy its r06_pmc.json to profiles/')
     assert d['chain']['pass1_bytes_per_solved_frame'] > 0 and d['lbs']['mesh_order']['bytes_per_call_at_4000_frames'] > 0

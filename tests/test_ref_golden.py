@@ -199,43 +199,25 @@ def test_surface_sign_matches_reference_direction_method():
     assert np.allclose(np.sqrt(d2) * G['surf_direction'], dist, rtol=0, atol=1e-15)
 
 
-def _s2m_ref():
-    """oracle/_ref/libs2m_ref.so: the reference's own sample2meshdist.h compiled in place (oracle/ref_build/Makefile)."""
-    import ctypes as C
-    import subprocess
-    so_path = os.path.join(os.path.dirname(GOLD), '..', 'oracle', '_ref', 'libs2m_ref.so')
-    so_path = os.path.abspath(so_path)
-    if not os.path.exists(so_path):
-        if not os.path.exists('/root/reference/src/moshpp/scan2mesh/mesh_distance/sample2meshdist.h'):
-            pytest.skip('reference sources not present and oracle/_ref not prebuilt')
-        subprocess.check_call(['make', '-C', os.path.join(os.path.dirname(so_path), '..', 'ref_build')])
-    lib = C.CDLL(so_path)
-    lib.s2m_ref_squared.restype = C.c_double
-    lib.s2m_ref_squared.argtypes = [C.c_int] + [C.POINTER(C.c_double)] * 8
-    return lib
-
-
 def test_surface_distance_derivatives_match_compiled_reference_header():
     """The oracle's closed-form gradients of the point-to-surface distance against the REFERENCE'S OWN C++ (sample2meshdist.h:67-205:
-    pointPlane / pointLine / pointPoint with Square), compiled from /root/reference in place: squared distance and its gradients wrt the
-    point and the triangle's vertices for every nearest-part code."""
-    import ctypes as C
+    pointPlane / pointLine / pointPoint with Square), compiled in place and executed by tests/golden/make_ref_s2m_golden.py on the
+    triangle and nearest part the oracle picks for each point (ref_s2m.npz): squared distance and its gradients wrt the point and the
+    triangle's vertices for every nearest-part code."""
     from oracle import stagei_oracle as s1
-    lib = _s2m_ref()
+    ref = np.load(os.path.join(GOLD, 'ref_s2m.npz'))
     si = ref_inputs.surface_inputs()
     v, f, pts = si['v'], si['f'], si['pts']
     dist, tri, part, dp, dabc, fv = s1.signed_surface_distance(pts, v, f, want_jac=True)
-    P = C.POINTER(C.c_double)
+    assert np.array_equal(part, ref['part']) and np.array_equal(fv, ref['tri_vertices'])     # the calls the fixture recorded
     seen = set()
     for i in range(len(pts)):
-        x = np.ascontiguousarray(pts[i]); a, b, c = [np.ascontiguousarray(v[k]) for k in fv[i]]
-        g = [np.zeros(3) for _ in range(4)]
-        d2 = lib.s2m_ref_squared(int(part[i]), *[z.ctypes.data_as(P) for z in (x, a, b, c)], *[z.ctypes.data_as(P) for z in g])
+        d2, g = ref['d2'][i], ref['grad'][i]
         seen.add(int(part[i]))
         assert abs(d2 - dist[i] ** 2) < 1e-15
         # ours: d(signed dist) = direction . d|dist|  ->  d(dist^2) = 2 dist . d(signed dist)
         assert np.abs(g[0] - 2 * dist[i] * dp[i]).max() < 1e-12
-        assert np.abs(np.array(g[1:]) - 2 * dist[i] * dabc[i]).max() < 1e-12
+        assert np.abs(g[1:] - 2 * dist[i] * dabc[i]).max() < 1e-12
     assert {0} < seen and len(seen) >= 3
 
 

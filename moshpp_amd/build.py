@@ -57,6 +57,13 @@ def needs_build():
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 
+def compile_flags(src, profile=False, defines=()):
+    """hipcc flags (other than -c / -o and the source hash) this build compiles one of SOURCES with; tests/kernels/build_probe.py builds
+    its single-kernel launchers around stagei.hip with the same ones."""
+    return (['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result', '-Wno-unused-value']
+            + (['-DMOSHII_PROFILE'] if profile else []) + list(defines) + EXTRA_FLAGS.get(src, []))
+
+
 def build(force=False, verbose=True, profile=False, variant=None, defines=()):
     """profile=True builds libmoshii_prof.so with in-kernel clock64() phase laps (tools/prof_chain.py).
     variant / defines: development builds libmoshii_<variant>[_prof].so with extra -D flags (kernel experiments; selected at run
@@ -73,8 +80,7 @@ def build(force=False, verbose=True, profile=False, variant=None, defines=()):
     procs = []
     for s in SOURCES:
         obj = os.path.join(CSRC, s.replace('.hip', f'{tag}.o'))
-        cmd = [_hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result', '-Wno-unused-value',
-               '-c', os.path.join(CSRC, s), '-o', obj] + (['-DMOSHII_PROFILE'] if profile else []) + list(defines) + EXTRA_FLAGS.get(s, []) + [f'-DMOSHII_SRC_HASH="{shash}"']
+        cmd = [_hipcc()] + compile_flags(s, profile, defines) + ['-c', os.path.join(CSRC, s), '-o', obj, f'-DMOSHII_SRC_HASH="{shash}"']
         if verbose:
             print(' '.join(cmd), flush=True)
         procs.append((s, subprocess.Popen(cmd)))

@@ -289,3 +289,43 @@ def test_mosh_stagei_matches_executed_reference(name, tmp_path):
                pose=np.array(dbg['opt_models_pose']), trans=np.array(dbg['opt_models_trans']), errs=dbg['stagei_errs'])
     assert np.all(res['betas'][sc['nb']:] == 0)
     check_stagei_against_reference_run(name, ref, got)
+
+
+def _stagei_job_oracle(pb):
+    from oracle import stageii_oracle as so, stagei_oracle as s1
+    m = so.prepare_model(pb['model'])
+    so.set_free_shape(m, 0, pb['nb'])
+    return s1.stagei_solve(m, pb['faces'], so.prepare_gmm_prior(pb['gmm'], 63), 'smplh', pb['frames'], pb['vids'],
+                           {'body': np.ones(pb['M'], bool)}, {'body': pb['skin']}, pb['nb'])
+
+
+def test_stagei_at_stated_size_matches_oracle():
+    """workload.make_stagei_job(): 12 frames, 53 markers, 10 betas, V = 6890, 925 unknowns -- the Stage-I problem bench.py times --
+    against the oracle, with test_stagei_matches_oracle's tolerances."""
+    from moshpp_amd import capi, workload
+    pb, dev, pr, kw = workload.make_stagei_job()
+    out = capi.stagei_solve_host(dev, pr, **kw)
+    ref = _stagei_job_oracle(pb)
+    print(f'stagei at the stated size: {out["iters"]} iterations')
+    assert np.abs(out['betas'] - ref['betas']).max() < 1e-5
+    assert np.abs(out['markers_latent'] - ref['markers_latent']).max() < 1e-6
+    assert np.abs(out['pose'] - ref['pose']).max() < 1e-5 and np.abs(out['trans'] - ref['trans']).max() < 1e-6
+    assert (out['markers_latent_vids'] == ref['markers_latent_vids']).all()
+    e = ref['errs']
+    want = dict(data=e['data'], poseB=e['poseB'], init=e['init_0'], beta=e['beta'], surf=e['surf'], poseH=e.get('poseH', 0.0))
+    for k, v in want.items():
+        assert abs(out['errs'][k] - v) <= 1e-5 * max(1.0, abs(v)), k
+
+
+def test_stagei_schur_solver_matches_dense_at_stated_size(monkeypatch):
+    """The arrow-structured solver against the dense blocked Cholesky on make_stagei_job(): ns = 3 x 53 + 10 = 169 shared unknowns, so the
+    Schur block's Cholesky ends in a partial (9-column) panel.  Equal iteration counts."""
+    from moshpp_amd import capi, workload
+    pb, dev, pr, kw = workload.make_stagei_job()
+    monkeypatch.setenv('MOSHII_S1_SOLVER', 'dense')
+    a = capi.stagei_solve_host(dev, pr, **kw)
+    monkeypatch.delenv('MOSHII_S1_SOLVER', raising=False)
+    b = capi.stagei_solve_host(dev, pr, **kw)
+    assert a['iters'] == b['iters']
+    assert np.abs(a['betas'] - b['betas']).max() < 1e-6 and np.abs(a['markers_latent'] - b['markers_latent']).max() < 1e-7
+    assert np.abs(a['pose'] - b['pose']).max() < 1e-6

@@ -22,7 +22,8 @@
  *   - unknowns per solve (3 + free pose variables + free shape coefficients): <= 127 without, <= 207 with a jaw term or a
  *     free shape block (n_face > 0 or n_shape > 0);
  *   - mixture components of the prior x npose must fit beside the Jacobian tiles: G = 8, npose <= 69 as the reference
- *     ships them; the marker-tile size adapts, a layout that cannot fit at all is reported as an error.
+ *     ships them for the human models, G = 1 / npose 81 (SMAL horse) and npose 93 (SMAL dog); npose <= 127 (the prior's
+ *     columns are two per lane); the marker-tile size adapts, a layout that cannot fit at all is reported as an error.
  */
 #ifndef MOSHII_H
 #define MOSHII_H
@@ -193,9 +194,16 @@ typedef struct moshii_solve_opts {
     double  wt_shape_stay;          /* DMPL: 6.0 = "extrap_dmpl" (:693-697).  dmpl_prev is refreshed (:658-659) before the
                                      * term is built, so it evaluates to (dmpl - dmpl at frame start) * 6 from the second
                                      * solved frame on.  0: no such term (expression).           */
+    /* SMAL horse joint-angle term "poseB_jangles" (chmosh.py:615-617, 640-643; prior/horse_body_prior.py):
+     * r_i = exp(pose[jangle_ids[i]])^2 * wt_poseB_annealed * wt_jangle, in every phase, with the first-frame rounds' prior weight
+     * there (10x, 5x, 1x).  0 / NULL = absent (every other model type).  Appended in version 102: a caller built against an older
+     * header must not pass its shorter struct to a 102 library -- check moshii_version() >= 102 and zero the struct first. */
+    int32_t n_jangle;               /* 12 for animal_horse: pose ids 6,7,8, 11,12,13, 20,21,22, 25,26,27 */
+    const int32_t* jangle_ids;
+    double  wt_jangle;              /* 2.0                                                        */
 } moshii_solve_opts;
 
-#define MOSHII_NERR 8               /* per-frame SSE columns: data, poseB, velo, poseH, poseF, shape, shape_stay, 0 */
+#define MOSHII_NERR 8               /* per-frame SSE columns: data, poseB, velo, poseH, poseF, shape, shape_stay, poseB_jangles */
 
 typedef struct moshii_chain_desc {
     moshii_attach_t attach;

@@ -41,10 +41,11 @@ class SolveOpts(C.Structure):
                 ('n_step1', C.c_int32), ('step1_ids', _c_int_p), ('n_step2', C.c_int32), ('step2_ids', _c_int_p),
                 ('n_body', C.c_int32), ('body_ids', _c_int_p), ('n_finger', C.c_int32), ('finger_ids', _c_int_p),
                 ('n_face', C.c_int32), ('face_ids', _c_int_p), ('wt_poseF', C.c_double), ('n_shape', C.c_int32),
-                ('wt_shape', C.c_double), ('wt_shape_stay', C.c_double)]
+                ('wt_shape', C.c_double), ('wt_shape_stay', C.c_double),
+                ('n_jangle', C.c_int32), ('jangle_ids', _c_int_p), ('wt_jangle', C.c_double)]
 
 
-NERR = 8   # MOSHII_NERR: data, poseB, velo, poseH, poseF, shape, shape_stay, 0
+NERR = 8   # MOSHII_NERR: data, poseB, velo, poseH, poseF, shape, shape_stay, poseB_jangles
 
 
 class ChainDesc(C.Structure):
@@ -292,10 +293,11 @@ class Attachment:
 
 
 def make_opts(weights, step1_ids, step2_ids, body_ids, finger_ids, maxiter=100, e3_first=1e-3, e3=1e-2,
-              delta0=0.5, num_train_markers=46.0, face_ids=(), n_shape=0, shape_kind=None):
+              delta0=0.5, num_train_markers=46.0, face_ids=(), n_shape=0, shape_kind=None, jangle_ids=(), wt_jangle=2.0):
     """SolveOpts + the arrays it points to (keep the returned tuple alive during the call).
     face_ids: jaw pose ids of optimize_face (also part of step2_ids); n_shape / shape_kind ('expr' | 'dmpl'): the free
-    shape block declared with Model.set_free_shape."""
+    shape block declared with Model.set_free_shape.  jangle_ids: the pose ids of the SMAL horse's joint-angle term
+    (chmosh.STAGEII_JANGLE_IDS), weighted wt_pose * wt_jangle; empty: no such term."""
     o = SolveOpts()
     o.wt_data = float(weights['stageii_wt_data']); o.wt_velo = float(weights['stageii_wt_velo'])
     o.wt_poseB = float(weights['stageii_wt_poseB']); o.wt_poseH = float(weights['stageii_wt_poseH'])
@@ -311,6 +313,10 @@ def make_opts(weights, step1_ids, step2_ids, body_ids, finger_ids, maxiter=100, 
         assert shape_kind in ('expr', 'dmpl')
         o.wt_shape = float(weights['stageii_wt_expr' if shape_kind == 'expr' else 'stageii_wt_dmpl'])
         o.wt_shape_stay = 6.0 if shape_kind == 'dmpl' else 0.0     # chmosh.py:697
+    if len(jangle_ids):
+        ja = np.ascontiguousarray(jangle_ids, dtype=np.int32)
+        arrs.append(ja)
+        o.n_jangle, o.jangle_ids, o.wt_jangle = len(ja), _ip(ja), float(wt_jangle)
     return o, arrs
 
 

@@ -18,13 +18,16 @@ import numpy as np
 from . import capi
 from .mocap_interface import MocapSession, general_labels_map   # (the alias table of chmosh.py:466: moshpp_amd/data/label_aliases.json)
 from .models import load_surface_model
-from .prior import create_gmm_body_prior
+from .prior import create_body_prior, create_gmm_body_prior, dog_pose_body_ids
 from .transformed_lm import TransformedCoeffs
 
 logger = logging.getLogger('moshpp_amd')
 
 NUM_TRAIN_MARKERS = 46   # chmosh.py:460
-ERR_KEYS = ('data', 'poseB', 'velo', 'poseH')
+ERR_KEYS = ('data', 'poseB', 'poseB_jangles', 'velo', 'poseH')   # poseB_jangles: animal_horse only
+# the SMAL horse's joint-angle prior (horse_body_prior.py smal_horse_joint_angle_prior): ids 6..27 of pose[pose_body_ids] + 3
+STAGEII_JANGLE_IDS = (6, 7, 8, 11, 12, 13, 20, 21, 22, 25, 26, 27)
+STAGEII_JANGLE_WT = 2.0   # opt_objs['poseB_jangles'] = ... * wt_pose * 2. (chmosh.py:615-617, 640-643)
 
 
 def _get(node, key, default=None):
@@ -66,6 +69,10 @@ def stageii_pose_ids(surface_model_type, pose_size, optimize_fingers, optimize_t
             pose_finger_ids = all_pose_ids[75:]
     elif surface_model_type == 'mano':
         pose_finger_ids = all_pose_ids[3:]
+    elif surface_model_type == 'animal_horse':
+        pose_body_ids = all_pose_ids[3:84]                  # disable_tail_mouth_ear (:572-573)
+    elif surface_model_type == 'animal_dog':
+        pose_body_ids = [all_pose_ids[i] for i in dog_pose_body_ids()]   # :574-579
     else:
         raise NotImplementedError(f'surface model type {surface_model_type}')
     step1 = pose_root_ids + pose_body_ids
@@ -146,9 +153,11 @@ class StageIISolver:
             if prior['npose'] != len(self.ids['body']):
                 raise ValueError(f"prior npose {prior['npose']} != len(pose_body_ids) {len(self.ids['body'])}")
             self.prior = capi.Prior(prior['means'], prior['chols'], prior['weights'])
+        self.jangle = self.model_type == 'animal_horse'
         self.opts = capi.make_opts(weights, self.ids['step1'], self.ids['step2'], self.ids['body'], self.ids['finger'],
                                    maxiter=maxiter, num_train_markers=NUM_TRAIN_MARKERS, face_ids=self.ids['face'],
-                                   n_shape=self.n_shape, shape_kind=self.shape_kind)
+                                   n_shape=self.n_shape, shape_kind=self.shape_kind,
+                                   jangle_ids=STAGEII_JANGLE_IDS if self.jangle else (), wt_jangle=STAGEII_JANGLE_WT)
         self.optimize_fingers = bool(optimize_fingers)
         self.optimize_face = bool(optimize_face)
         self.optimize_dynamics = bool(optimize_dynamics)
@@ -251,9 +260,8 @@ def mosh_stageii(mocap_fname: str, cfg, markers_latent: np.ndarray, latent_label
                             v_template_fname=v_template_fname)
     assert sm.model_type == cfg.surface_model.type, ValueError(f'{sm.model_type} != {cfg.surface_model.type}')
     prior = None
-    if cfg.moshpp.pose_body_prior_fname and sm.model_type != 'mano':
-        prior = create_gmm_body_prior(cfg.moshpp.pose_body_prior_fname,
-                                      exclude_hands=sm.model_type in ['smplh', 'smplx'])
+    if cfg.moshpp.pose_body_prior_fname:     # by type (bodymodel_loader.py:121-135): SMAL horse / dog priors, else the human GMM
+        prior = create_body_prior(sm.model_type, cfg.moshpp.pose_body_prior_fname)
     stageii_wts = cfg.opt_settings.weights
     ext = _get(cfg, 'moshpp_amd', {}) or {}
     dmpl_pcs = None
@@ -312,6 +320,8 @@ def mosh_stageii(mocap_fname: str, cfg, markers_latent: np.ndarray, latent_label
     errs = {'data': out['errs'][solved, 0]}
     if len(solver.ids['body']):
         errs['poseB'] = out['errs'][solved, 1]
+        if solver.jangle:
+            errs['poseB_jangles'] = out['errs'][solved, 7]
     if len(solved) > 2:
         errs['velo'] = out['errs'][solved[2:], 2]   # the velocity term exists from the third solved frame on
     if solver.optimize_fingers:
@@ -383,6 +393,9 @@ def mosh_stagei(stagei_frames, cfg, betas_fname=None, v_template_fname=None) -> 
     (:103-137) and returned dict (:432-455).  `stagei_frames`: list of `label -> xyz` dicts, one per picked frame
     (frame_picker.load_marker_sessions_*).  The joint solve runs in libmoshii (moshii_stagei_solve, HIP); no CPU fallback."""
     from .marker_layout import marker_layout_load
+    if str(cfg.surface_model.type).startswith('animal'):
+        raise NotImplementedError(f'Stage-I is not implemented for {cfg.surface_model.type}: Stage-II (mosh_stageii) accepts the betas and '
+                                  f'latent markers of a Stage-I result made elsewhere')
     betas = None
     if betas_fname is not None:
         logger.debug(f'loading pre-computed betas: {betas_fname}')

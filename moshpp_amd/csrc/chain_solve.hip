@@ -88,6 +88,7 @@ struct FrameParams {
     int v0, v1;             // the entries [v0, v1) of the visible-marker list whose Jacobian rows are built here (plain chain: all of them)
 };
 
+// hand: the finger term's SSE -- or, in a solve with the joint-angle term (an animal: no fingers), that term's (MOSHII_NERR column 7)
 struct Sse { double data, prior, velo, hand, total, face, shape, stay; };
 
 // Cross-lane moves on the DPP path (a v_mov per 32-bit half: no LDS crossbar round trip as with ds_bpermute).
@@ -892,6 +893,14 @@ __device__ Sse eval_forward(const Ctx& cx, const ModelDev& md, const AttachDev& 
                 ss += d * d;
                 if (fp.has_stay) { const double d2 = (sv_ - cx.shp0[e]) * op.wt_shape_stay; sy += d2 * d2; }
             }
+    }
+    // joint-angle term of the SMAL horse (horse_body_prior.py smal_horse_joint_angle_prior, chmosh.py:615-617, 640-643):
+    // r_i = exp(pose[p_i])^2 * wt_pose * 2 with the phase's (first-frame: annealed) prior weight.  Every rank of a cooperative chain holds
+    // the same pose and evaluates it for itself, as it does the velocity and finger terms: no exchange carries it.  Its sum rides in the
+    // finger term's accumulator (a model with this term has no finger ids): no reduction, field or barrier of its own.
+    if (op.njangle > 0) {
+        const double wj = fp.wt_pose * op.wt_jangle;
+        for (int i = tid; i < op.njangle; i += MOSHII_TPB) { const double e = exp(pose[op.jangle[i]]); const double r = (e * e) * wj; sh += r * r; }
     }
     PROF_LAP(40);
     // F7: prior: l_g = sqrt(.5) (x - mu_g) . L_g for every component, argmin of |l_g|^2 - log w_g
@@ -2504,6 +2513,14 @@ __device__ void assemble(const Ctx& cx, const ChainLayout& ly, const ModelDev& m
                     const double w2 = fp.wt_poseF * fp.wt_poseF; dg += w2; gq -= w2 * pose[pid];
                 }
             }
+            // joint-angle term: d r_i / d x = 2 r_i, one row per id, so a diagonal entry and a gradient entry on its free column
+            if (op.njangle > 0)
+                for (int i = 0; i < op.njangle; ++i)
+                    if (op.jangle[i] == pid) {
+                        const double e = exp(pose[pid]);
+                        const double r = (e * e) * (fp.wt_pose * op.wt_jangle), d = 2.0 * r;
+                        dg += d * d; gq -= d * r;
+                    }
         }
         dvec[q] = dg;
         cx.g[q] += gq;
@@ -3508,8 +3525,9 @@ __global__ __launch_bounds__(MOSHII_TPB, MINW) void k_chain_solve(const ChainDev
             if (tid == 0 && lead) {
                 if ((o = chp->trans) != nullptr) { o[t * 3 + 0] = cx.trans[0]; o[t * 3 + 1] = cx.trans[1]; o[t * 3 + 2] = cx.trans[2]; }
                 if ((o = chp->errs) != nullptr) {
-                    o[t * 8 + 0] = fin.data; o[t * 8 + 1] = fin.prior; o[t * 8 + 2] = fin.velo; o[t * 8 + 3] = fin.hand;
-                    o[t * 8 + 4] = XT ? fin.face : 0.0; o[t * 8 + 5] = XT ? fin.shape : 0.0; o[t * 8 + 6] = XT ? fin.stay : 0.0; o[t * 8 + 7] = 0.0;
+                    const bool ja = op.njangle > 0;
+                    o[t * 8 + 0] = fin.data; o[t * 8 + 1] = fin.prior; o[t * 8 + 2] = fin.velo; o[t * 8 + 3] = ja ? 0.0 : fin.hand;
+                    o[t * 8 + 4] = XT ? fin.face : 0.0; o[t * 8 + 5] = XT ? fin.shape : 0.0; o[t * 8 + 6] = XT ? fin.stay : 0.0; o[t * 8 + 7] = ja ? fin.hand : 0.0;
                 }
                 int* oi;
                 if ((oi = chp->iters) != nullptr) { oi[t * 2 + 0] = n_iter; oi[t * 2 + 1] = n_fev; }
@@ -3616,6 +3634,7 @@ __global__ __launch_bounds__(MOSHII_TPB) void k_markers(const AttachDev* __restr
     op.nbody = 0; op.nfinger = 0; op.n1 = 0; op.n2 = 0; op.maxiter = 0;
     op.step1 = nullptr; op.step2 = nullptr; op.body = nullptr; op.finger = nullptr;
     op.nface = 0; op.nshape = 0; op.face = nullptr;
+    op.njangle = 0; op.wt_jangle = 0.0; op.jangle = nullptr;
     for (int k = 1 + tid; k < md.K; k += MOSHII_TPB) cx.ksum[k - 1] = k;   // every joint's correctives, on top of v_shaped
     for (int i = tid; i < 3 * md.K; i += MOSHII_TPB) cx.Jl[i] = md.J[i];
     __syncthreads();

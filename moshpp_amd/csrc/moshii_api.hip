@@ -335,7 +335,7 @@ struct LaunchInfo { std::string name; int lds = 0; int threads = 0; } g_last;
 extern "C" {
 
 const char* moshii_last_error(void) { return g_err.c_str(); }
-int moshii_version(void) { return 101; }   // 101: moshii_stagei_desc grew by init_sq (include/moshii.h)
+int moshii_version(void) { return 102; }   // 101: moshii_stagei_desc grew by init_sq; 102: moshii_solve_opts by the joint-angle term (include/moshii.h)
 #ifndef MOSHII_SRC_HASH
 #define MOSHII_SRC_HASH "unknown"
 #endif
@@ -544,6 +544,7 @@ int moshii_lbs_forward_f32(moshii_model_t m, int32_t F, const float* pose, const
 int moshii_prior_create(int32_t G, int32_t npose, const double* means, const double* chols, const double* weights,
                         moshii_prior_t* out) {
     if (!means || !chols || !weights || !out || G < 1 || npose < 1) return fail(MOSHII_ERR_ARG, "bad argument");
+    if (npose > 127) return fail(MOSHII_ERR_UNSUPPORTED, "prior npose > 127 (the chain kernel takes a prior's columns two per lane)");
     if (moshii_device_count() < 1) return fail(MOSHII_ERR_NO_DEVICE, "no HIP device: libmoshii has no CPU path");
     auto* p = new moshii_prior_s();
     p->G = G; p->npose = npose;
@@ -761,6 +762,11 @@ int prepare_launch(moshii_model_t m, moshii_prior_t prior, const moshii_solve_op
     if (o->n_face > 0 && !o->face_ids) return fail(MOSHII_ERR_ARG, "face_ids missing");
     for (int i = 1; i < o->n_face; ++i)
         if (o->face_ids[i] != o->face_ids[i - 1] + 1) return fail(MOSHII_ERR_UNSUPPORTED, "face ids must be contiguous");
+    if (o->n_jangle < 0 || (o->n_jangle > 0 && !o->jangle_ids)) return fail(MOSHII_ERR_ARG, "bad joint-angle term");
+    for (int i = 0; i < o->n_jangle; ++i)
+        if (o->jangle_ids[i] < 0 || o->jangle_ids[i] >= NP) return fail(MOSHII_ERR_ARG, "joint-angle id out of range");
+    if (o->n_jangle > 0 && o->n_finger > 0)   // (the kernel sums the joint-angle term in the finger term's accumulator)
+        return fail(MOSHII_ERR_UNSUPPORTED, "a joint-angle term and finger ids in one solve (no SMAL model has fingers)");
     const int xt = (nshape > 0 || o->n_face > 0) ? 1 : 0;
     const int nmax = 3 + std::max(o->n_step1, o->n_step2 + nshape);
     int nblk = pick_nblk(nmax, xt != 0);
@@ -856,7 +862,8 @@ int prepare_launch(moshii_model_t m, moshii_prior_t prior, const moshii_solve_op
     const size_t lds_bytes = (size_t)ly.total_doubles * sizeof(double);
     if (lds_bytes > 160 * 1024) return fail(MOSHII_ERR_UNSUPPORTED, "problem does not fit the 160 KiB LDS of a CU");
 
-    const size_t nids = (size_t)o->n_step1 + o->n_step2 + o->n_body + o->n_finger + o->n_face;
+    const int njangle = std::max(0, o->n_jangle);
+    const size_t nids = (size_t)o->n_step1 + o->n_step2 + o->n_body + o->n_finger + o->n_face + njangle;
     const size_t need = sizeof(int) * (nids + 16) + 64 + extra_bytes;
     int rc = m->scratch.reserve(need);
     if (rc) return rc;
@@ -869,6 +876,8 @@ int prepare_launch(moshii_model_t m, moshii_prior_t prior, const moshii_solve_op
     ids.insert(ids.end(), o->finger_ids, o->finger_ids + o->n_finger);
     const size_t efc = ids.size();
     ids.insert(ids.end(), o->face_ids, o->face_ids + o->n_face);
+    const size_t eja = ids.size();
+    if (njangle > 0) ids.insert(ids.end(), o->jangle_ids, o->jangle_ids + njangle);
     char* dbase = m->scratch.ptr;
     if (!ids.empty()) {
         HIP_TRY(hipMemcpyAsync(dbase, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice, stream));
@@ -887,6 +896,7 @@ int prepare_launch(moshii_model_t m, moshii_prior_t prior, const moshii_solve_op
     od.nface = o->n_face; od.nshape = nshape;
     const int* dids = (const int*)dbase;
     od.step1 = as_gp(dids + e1); od.step2 = as_gp(dids + e2); od.body = as_gp(dids + eb); od.finger = as_gp(dids + ef); od.face = as_gp(dids + efc);
+    od.njangle = njangle; od.wt_jangle = njangle > 0 ? o->wt_jangle : 0.0; od.jangle = as_gp(dids + eja);
     memset(&cfg->pd, 0, sizeof(cfg->pd));
     if (prior) cfg->pd = prior->dev();
     cfg->md = m->dev();

@@ -82,6 +82,10 @@ struct OptsDev {
     double wt_poseF, wt_shape, wt_shape_stay;
     int nface, nshape;
     MOSHII_GP(const int) face;
+    // SMAL horse joint-angle term (both kernel variants): r_i = wt_jangle * wt_pose * exp(pose[jangle[i]])^2; njangle = 0: absent
+    int njangle;
+    double wt_jangle;
+    MOSHII_GP(const int) jangle;
 };
 
 // Cooperative chains (chain_solve.hip, COOP variant): ONE chain solved by G workgroups = G CUs.  Every rank holds the whole solver state

@@ -20,7 +20,7 @@ import numpy as np
 
 MODEL_TYPE_BY_NJOINT_PARMS = {69: 'smpl', 153: 'smplh', 162: 'smplx', 45: 'mano', 105: 'animal_horse',
                               102: 'animal_dog'}   # smpl_fast_derivatives.py:66-67
-SUPPORTED_TYPES = ('smpl', 'smplh', 'smplx', 'mano')
+SUPPORTED_TYPES = ('smpl', 'smplh', 'smplx', 'mano', 'animal_horse', 'animal_dog')   # animals: SMAL, Stage-II only
 
 
 class _ChStandIn:

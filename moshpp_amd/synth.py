@@ -17,7 +17,28 @@ MODEL_DIMS = {  # V, K   (smpl_fast_derivatives.py:63-68 infers the type from po
     'smplh': (6890, 52),
     'smplx': (10475, 55),
     'mano': (778, 16),
+    # SMAL quadrupeds (posedirs width 315 / 306 -> smpl_fast_derivatives.py:66-67); 3889 vertices as SMAL has.  Synthetic: a procedural
+    # quadruped (spine, four legs, neck, head, jaw, ears, tail) of those sizes, not the SMAL mesh or skeleton.
+    'animal_horse': (3889, 36),
+    'animal_dog': (3889, 35),
 }
+
+# the synthetic quadruped: (parent, rest position) per joint; the horse has all 36, the dog the first 35
+_QUAD_JOINTS = [
+    (-1, (0.00, 0.00, 0.00)),                                                                    # 0 root (pelvis)
+    (0, (0.15, 0.02, 0.0)), (1, (0.30, 0.03, 0.0)), (2, (0.45, 0.03, 0.0)), (3, (0.60, 0.03, 0.0)), (4, (0.75, 0.05, 0.0)),   # 1-5 spine
+    (5, (0.80, -0.10, 0.15)), (6, (0.80, -0.45, 0.15)), (7, (0.80, -0.80, 0.15)), (8, (0.80, -1.15, 0.15)),        # 6-9 left fore leg
+    (5, (0.80, -0.10, -0.15)), (10, (0.80, -0.45, -0.15)), (11, (0.80, -0.80, -0.15)), (12, (0.80, -1.15, -0.15)),  # 10-13 right fore leg
+    (5, (0.95, 0.20, 0.0)), (14, (1.10, 0.45, 0.0)), (15, (1.25, 0.65, 0.0)),                                         # 14-16 neck, head
+    (0, (-0.10, -0.10, 0.15)), (17, (-0.10, -0.45, 0.15)), (18, (-0.10, -0.80, 0.15)), (19, (-0.10, -1.15, 0.15)),  # 17-20 left hind leg
+    (0, (-0.10, -0.10, -0.15)), (21, (-0.10, -0.45, -0.15)), (22, (-0.10, -0.80, -0.15)), (23, (-0.10, -1.15, -0.15)),  # 21-24 right hind
+    (0, (-0.20, -0.06, 0.0)), (25, (-0.30, -0.12, 0.0)), (26, (-0.40, -0.18, 0.0)), (27, (-0.50, -0.24, 0.0)),   # 25-31 tail
+    (28, (-0.60, -0.30, 0.0)), (29, (-0.70, -0.36, 0.0)), (30, (-0.80, -0.42, 0.0)),
+    (16, (1.45, 0.60, 0.0)), (16, (1.25, 0.80, 0.06)), (16, (1.25, 0.80, -0.06)),                                   # 32 jaw, 33-34 ears
+    (32, (1.60, 0.55, 0.0)),                                                                                          # 35 mouth tip (horse)
+]
+_QUAD_RADIUS = {0: 0.25, 1: 0.25, 2: 0.25, 3: 0.25, 4: 0.25, 5: 0.22, 6: 0.12, 10: 0.12, 17: 0.12, 21: 0.12, 14: 0.12, 15: 0.11, 16: 0.10,
+                32: 0.05, 33: 0.02, 34: 0.02, 35: 0.04}
 
 _SMPL_BODY_PARENTS = [-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19]
 _HAND_LOCAL = [-1, 0, 1, -1, 3, 4, -1, 6, 7, -1, 9, 10, -1, 12, 13]  # -1 = wrist
@@ -39,6 +60,8 @@ def kintree_parents(model_type):
         return np.array(p, dtype=np.int64)
     if model_type == 'mano':
         return np.array([-1] + [0 if q < 0 else 1 + q for q in _HAND_LOCAL], dtype=np.int64)
+    if model_type in ('animal_horse', 'animal_dog'):
+        return np.array([p for p, _ in _QUAD_JOINTS[:MODEL_DIMS[model_type][1]]], dtype=np.int64)
     raise ValueError(model_type)
 
 
@@ -78,10 +101,16 @@ def rest_joints(model_type):
                           _hand_joints(_BODY_JOINTS[21], -1.0)])
     if model_type == 'mano':
         return np.vstack([[[0.0, 0.0, 0.0]], _hand_joints(np.zeros(3), 1.0)])
+    if model_type in ('animal_horse', 'animal_dog'):
+        scale = 1.0 if model_type == 'animal_horse' else 0.45
+        return scale * np.array([x for _, x in _QUAD_JOINTS[:MODEL_DIMS[model_type][1]]], dtype=np.float64)
     raise ValueError(model_type)
 
 
 def _bone_radius(model_type, j, K):
+    if model_type in ('animal_horse', 'animal_dog'):
+        r = _QUAD_RADIUS.get(j, 0.06 if j < 25 else 0.03)
+        return r if model_type == 'animal_horse' else 0.45 * r
     if model_type == 'mano':
         return 0.030 if j == 0 else 0.009
     body_r = {0: 0.13, 1: 0.08, 2: 0.08, 3: 0.13, 4: 0.06, 5: 0.06, 6: 0.14, 7: 0.045, 8: 0.045, 9: 0.14,
@@ -172,6 +201,8 @@ def _skin_and_blend(model_type, v_template, J0, seg_a, seg_b, rad, rng, num_beta
     for k in range(1, K):
         d2 = ((v_template - J0[k]) ** 2).sum(1)
         sig = 0.10 if model_type != 'mano' else 0.02
+        if model_type == 'animal_dog':
+            sig = 0.05
         g = 0.002 * np.exp(-d2 / (2 * sig * sig)) + 2e-5
         posedirs[:, :, 9 * (k - 1):9 * k] = g[:, None, None] * rng.normal(0, 1, (V, 3, 9))
 
@@ -348,6 +379,61 @@ def synth_gmm_prior(seed=0, n_gaussians=8, npose_full=69):
     return dict(means=means, covars=covars, weights=w / w.sum())
 
 
+def synth_horse_prior(seed=0, npose_full=105):
+    """Contents of a SMAL horse prior pickle (horse_body_prior.py smal_horse_prior): 'pic' [105, 105], a square root of a precision --
+    dense, NOT triangular, as a PCA-whitening matrix is -- and 'mean_pose' [105] (pose without the root).  The means of the joint-angle
+    entries (STAGEII_JANGLE_IDS - 3) lie where the quadruped motion keeps those angles."""
+    rng = np.random.default_rng(seed + 2323)
+    q, _ = np.linalg.qr(rng.normal(0, 1, (npose_full, npose_full)))
+    ev = np.exp(rng.uniform(np.log(0.02), np.log(0.3), npose_full))
+    pic = (q / np.sqrt(ev)).dot(np.linalg.qr(rng.normal(0, 1, (npose_full, npose_full)))[0])   # pic pic^T = cov^-1
+    mean_pose = rng.normal(0, 0.1, npose_full)
+    mean_pose[np.array(QUAD_JANGLE_IDS) - 3] += QUAD_JANGLE_OFFSET
+    return dict(pic=pic, mean_pose=mean_pose)
+
+
+def synth_dog_prior(seed=0, n_gaussians=4, npose_full=105):
+    """Contents of a SMAL dog prior pickle (dog_body_prior.py MaxMixtureDog): 'gmm_means' [G, 105], 'gmm_covs' [G, 105, 105],
+    'gmm_weights' [G]."""
+    rng = np.random.default_rng(seed + 3131)
+    means = rng.normal(0, 0.1, (n_gaussians, npose_full))
+    covs = np.zeros((n_gaussians, npose_full, npose_full))
+    for g in range(n_gaussians):
+        q, _ = np.linalg.qr(rng.normal(0, 1, (npose_full, npose_full)))
+        ev = np.exp(rng.uniform(np.log(0.02), np.log(0.3), npose_full))
+        covs[g] = (q * ev).dot(q.T)
+        covs[g] = 0.5 * (covs[g] + covs[g].T)
+    w = rng.uniform(0.5, 1.5, n_gaussians)
+    return dict(gmm_means=means, gmm_covs=covs, gmm_weights=w / w.sum())
+
+
+# the horse's joint-angle prior entries (chmosh.STAGEII_JANGLE_IDS) and where the quadruped motion keeps them: exp(2 x) of the term
+# is then ~0.3, not 1 -- a bent leg, as the prior intends
+QUAD_JANGLE_IDS = (6, 7, 8, 11, 12, 13, 20, 21, 22, 25, 26, 27)
+QUAD_JANGLE_OFFSET = -0.6
+
+
+def synth_quadruped_motion(NP, n_frames, seed=0, fps=120.0, amp=0.25, ramp=60):
+    """Smooth ground-truth pose[F, NP] and trans[F, 3] of a walking quadruped: sinusoid mixtures around a rest pose whose joint-angle
+    entries sit at QUAD_JANGLE_OFFSET, a forward root translation with a little bounce.  Pose ids 30:36 stay zero (the reference never frees
+    them unless optimize_toes)."""
+    rng = np.random.default_rng(seed + 27182)
+    t = np.arange(n_frames) / fps
+    pose = np.zeros((n_frames, NP))
+    for d in range(NP):
+        a = amp * rng.uniform(0.2, 1.0) * (0.6 if d < 3 else 1.0)
+        acc = np.zeros(n_frames)
+        for _ in range(3):
+            acc += rng.uniform(0.3, 1.0) * np.sin(2 * np.pi * rng.uniform(0.1, 1.2) * t + rng.uniform(0, 2 * np.pi))
+        pose[:, d] = a * acc / 2.0
+    pose *= np.clip(np.arange(n_frames) / float(max(ramp, 1)), 0.15, 1.0)[:, None]
+    pose[:, list(QUAD_JANGLE_IDS)] += QUAD_JANGLE_OFFSET
+    pose[:, 30:36] = 0.0
+    trans = np.stack([0.5 * t + 0.1 * np.sin(2 * np.pi * 0.2 * t), 1.2 + 0.03 * np.sin(2 * np.pi * 1.5 * t),
+                      0.3 * np.sin(2 * np.pi * 0.05 * t + 0.4)], axis=1)
+    return pose, trans
+
+
 # ------------------------------------------------------------------------------------------
 # tiny NumPy LBS used only to synthesise observations
 # ------------------------------------------------------------------------------------------
@@ -412,7 +498,7 @@ def pick_marker_vids(dd, n_markers, seed=0, body_only=True):
     v = dd['v_template']
     dom = np.argmax(dd['weights'], axis=1)
     cand = np.arange(v.shape[0])
-    if body_only and dd['model_type'] != 'mano':
+    if body_only and dd['model_type'] not in ('mano', 'animal_horse', 'animal_dog'):
         cand = cand[dom[cand] <= 21]
     first = cand[rng.integers(len(cand))]
     chosen = [first]
@@ -492,7 +578,10 @@ def make_sequence(model_type='smplh', n_frames=120, n_markers=53, seed=0, noise=
     markers_latent = can_body[vids] + dd['_outward'][vids] * 0.0095
     labels = [f'MK{idx:02d}' for idx in range(n_markers)]
     closest, coef = attach_markers(can_body, markers_latent)
-    pose_gt, trans_gt = synth_motion(NP, body_dof, n_frames, seed=seed if motion_seed is None else motion_seed)
+    if model_type in ('animal_horse', 'animal_dog'):
+        pose_gt, trans_gt = synth_quadruped_motion(NP, n_frames, seed=seed if motion_seed is None else motion_seed)
+    else:
+        pose_gt, trans_gt = synth_motion(NP, body_dof, n_frames, seed=seed if motion_seed is None else motion_seed)
     if motion_seed is not None:
         rng = np.random.default_rng(motion_seed + 5)
     if not (model_type in ('smplh', 'smplx') and not body_only_markers) and model_type != 'mano':
@@ -519,10 +608,15 @@ def make_sequence(model_type='smplh', n_frames=120, n_markers=53, seed=0, noise=
                        marker_type={l: 'body' for l in labels},
                        marker_type_mask={'body': np.ones(n_markers, dtype=bool)},
                        m2b_distance={'body': 0.0095}, surface_model_type=model_type)
-    return dict(model=dd, hand_prior=hand_prior, gmm=gmm, betas=betas, markers_latent=markers_latent,
-                latent_labels=labels, marker_meta=marker_meta, markers=markers, labels=list(labels),
-                frame_rate=120.0, pose_gt=pose_gt, trans_gt=trans_gt, model_type=model_type,
-                dof_per_hand=dof_per_hand, use_hands_mean=use_hands_mean, num_betas=num_betas)
+    out = dict(model=dd, hand_prior=hand_prior, gmm=gmm, betas=betas, markers_latent=markers_latent,
+               latent_labels=labels, marker_meta=marker_meta, markers=markers, labels=list(labels),
+               frame_rate=120.0, pose_gt=pose_gt, trans_gt=trans_gt, model_type=model_type,
+               dof_per_hand=dof_per_hand, use_hands_mean=use_hands_mean, num_betas=num_betas)
+    if model_type == 'animal_horse':
+        out['animal_prior'] = synth_horse_prior(seed)       # the pickle contents of the type's pose prior (own generators: the draws
+    elif model_type == 'animal_dog':                         # above are those of every other model type)
+        out['animal_prior'] = synth_dog_prior(seed)
+    return out
 
 
 # ------------------------------------------------------------------------------------------

@@ -19,8 +19,15 @@ parallel.partition_units (BASELINE config 3's shape; N = 1 is the `many_sequence
 into frame ranges with verified hand-offs (parallel.solve_sequence_sharded; config 5's shape).  `--scaling strong` makes the
 32-sequence job the headline (`value`, `scaling: "strong"`).
 
+A plain run does what its headline needs and nothing more: set-up (the seeded sequences are generated side by side, one host
+process each), --warmup untimed and --steps timed steps, the outputs of --dump-outputs, the line.  Its extra objects are `roofline`,
+computed from the timed steps themselves, and `chunking` / `seeds`; at N > 1 the headline job `strong.many_sequences`.  Every other
+leg below takes runs of its own and is measured only with `--full` (the `--no-...` options leave single legs out of it).
+
 Rank 0 prints ONE JSON line.  Extra objects:
   roofline           dominant kernel k_chain_solve against the f64 vector peak (it is latency/ALU-bound, not HBM-bound)
+  --full only:
+  plain_sweeps       every timed seed once more with one-workgroup repair chains
   roofline_lbs       the full-mesh LBS export kernel against the HBM peak
   cpu_baseline       the NumPy oracle ("port") on bounded samples, host cores of this box: one core in its lean mode (`value`),
                      one core doing the reference's own amount of work per iteration (`reference_cost`: full-mesh forward + dense
@@ -30,7 +37,7 @@ Rank 0 prints ONE JSON line.  Extra objects:
   incl_host_staging  the same solve through host buffers (observations in, results out over PCIe)
   many_sequences     32 sequences in one call: the dominant kernel with every CU busy
   config3            BASELINE config 3 as stated (32 x 4000 SMPL-X frames, 89 markers, fingers + jaw + 80 expressions free: 194 unknowns)
-  strong             the fixed jobs above, at this N
+  strong             the fixed jobs above, at this N (and rank 0 alone on the many-sequence job: `one_gpu_same_job`)
   stagei             Stage-I on 12 frames / 53 markers / 10 betas: GPU seconds (dense and arrow-structured solver), iterations, and
                      the NumPy oracle's seconds + differences on the same problem
 The reference / CPU / Stage-I legs run at N = 1 only.
@@ -230,6 +237,15 @@ def solver_flops(K, Nv, n1, n2, NP, npose, nobs_mean, iters, fevals):
     return float(fevals) * fwd + float(iters) * per_iter
 
 
+def _job_worker(a):
+    """One seeded sequence of the timed steps (workload.make_job: seconds of NumPy each), made in a host process of its own so that
+    the sequences are generated side by side; the job comes back pickled, equal to the bit to one made in the bench process."""
+    seed, frames, markers = a
+    sys.path.insert(0, ROOT)
+    from moshpp_amd import workload
+    return workload.make_job('smplh', n_frames=frames, n_markers=markers, seed=seed)
+
+
 def _cpu_chain_worker(a):
     """One oracle chain on `frames` frames of the seeded workload (a process of the all-cores CPU leg)."""
     seed, frames, markers = a
@@ -303,6 +319,9 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--frames', type=int, default=4000)
     ap.add_argument('--markers', type=int, default=53)
+    ap.add_argument('--full', action='store_true',
+                    help='also measure every leg beyond the headline (CPU baselines, parity against the oracle, the sequential chain, host '
+                         'staging, the fixed jobs, config 3, the LBS export roofline, Stage-I); a plain run times the headline alone')
     ap.add_argument('--mode', choices=('chunked', 'sequential'), default='chunked')
     ap.add_argument('--scaling', choices=('auto', 'weak', 'strong'), default='auto',
                     help='strong: the fixed many-sequence job (sequences dealt to the ranks) is the headline; weak: every rank its own copies of '
@@ -311,7 +330,7 @@ def main():
     ap.add_argument('--chunks', type=int, default=0, help='chunks per sequence (0 = one per CU)')
     ap.add_argument('--chunk-warmup', type=int, default=32)
     # hand-off tolerance: 1e-9 rad / m yields the same stitched result as 1e-11 (max deviation from the sequential chain 1.4e-9
-    # rad on all 4000 frames, re-measured below every run) with fewer repairs of warm-ups that were converged to 1e-10
+    # rad on all 4000 frames, re-measured below in every --full run) with fewer repairs of warm-ups that were converged to 1e-10
     ap.add_argument('--verify-tol', type=float, default=1e-9)
     ap.add_argument('--cpu-sample', type=int, default=240, help='frames of the workload timed on the CPU oracle (one core, lean mode)')
     ap.add_argument('--cpu-procs', type=int, default=0, help='processes of the all-cores CPU leg (0 = min(host cores, 32))')
@@ -350,6 +369,14 @@ def main():
     sys.stdout.flush()
     _real_stdout = os.dup(1)
     os.dup2(2, 1)
+
+    # the seeded sequences of the timed steps: one host process each, generating while torch and the device come up
+    t_start = time.perf_counter()
+    seeds = [int(x) for x in args.seeds.split(',') if x.strip()]
+    job_seeds = list(dict.fromkeys(seeds))
+    import multiprocessing as mp
+    job_pool = mp.get_context('spawn').Pool(len(job_seeds))
+    jobs_made = job_pool.map_async(_job_worker, [(sd, args.frames, args.markers) for sd in job_seeds])
 
     import torch
     rank = int(os.environ.get('RANK', '0'))
@@ -390,10 +417,11 @@ def main():
     lib = capi.load()
     capi.check(lib.moshii_set_device(local_rank))
     dev = torch.device('cuda', local_rank)
-    seeds = [int(x) for x in args.seeds.split(',') if x.strip()]
 
     # ---- workload: BASELINE config[1], one resident sequence per seed (same model / betas layout, different motion)
-    jobs = {sd: workload.make_job('smplh', n_frames=args.frames, n_markers=args.markers, seed=sd) for sd in seeds}
+    jobs = dict(zip(job_seeds, jobs_made.get()))
+    job_pool.close()
+    job_pool.join()
     solvers = {sd: workload.make_solver(jobs[sd]) for sd in seeds}
     seqs = {sd: workload.DeviceSequence(jobs[sd], solvers[sd], dev) for sd in seeds}
     job, solver, ds = jobs[seeds[0]], solvers[seeds[0]], seqs[seeds[0]]
@@ -428,8 +456,8 @@ def main():
         """The fixed many-sequence job: --strong-sequences DISTINCT captures of the seed-1000 subject (sequences of one subject share the
         model / prior handles of a call; capture i is motion seed 5000 + i through workload.make_capture -- the job waits for its hardest
         sequence, as a real batch does), dealt to the ranks by longest-processing-time; a rank solves its share in ONE
-        moshii_sequence_solve call.  On several GPUs rank 0 first solves the WHOLE job alone (the other ranks wait), so that the line
-        carries the one-GPU time of the same job on the same box.  Returns (frames solved here, seconds here, sequences here,
+        moshii_sequence_solve call.  On several GPUs and with --full, rank 0 first solves the WHOLE job alone (the other ranks wait), so
+        that the line carries the one-GPU time of the same job on the same box.  Returns (frames solved here, seconds here, sequences here,
         one-GPU seconds or None, one-GPU frames)."""
         shares = strong_job_shares(args.strong_sequences, F, world)
         share = shares[rank]
@@ -456,7 +484,7 @@ def main():
             return dt, sum(int((c.results()['status'] != 1).sum()) for c in copies)
 
         t_one, n_one = None, 0
-        if world > 1:
+        if world > 1 and args.full:
             if rank == 0:
                 t_one, n_one = solve(list(range(args.strong_sequences)))
             barrier()
@@ -514,6 +542,7 @@ def main():
         else:
             seqs[sd].solve_sequential(stream)
 
+    t_ready = time.perf_counter()
     for k in range(max(args.warmup, 0)):
         step(k)
     for sd in seeds:
@@ -527,6 +556,7 @@ def main():
         ev[k][1].record()
     torch.cuda.synchronize()
     t_local = time.perf_counter() - t0
+    t_steps_end = time.perf_counter()
     barrier()
     step_ms = np.array([a.elapsed_time(b) for a, b in ev])
     t_max = allmax(t_local)
@@ -576,7 +606,7 @@ def main():
         result['default_mode_frames_per_s'] = round(value, 1)
     if rep:
         result['chunking'] = dict(rep, repaired_per_step=float(np.mean([r['n_repaired'] for sd in used for r in reports[sd]])))
-    if args.mode == 'chunked' and world == 1:
+    if args.full and args.mode == 'chunked' and world == 1:
         # the same steps with PLAIN repair chains carried on inside the first launch (rounds 2-3's scheme; MOSHII_COOP_GROUP(1)), once per
         # seed, beside the timed default (cooperative sweeps from the host's rounds where the solve allows)
         tps = {}
@@ -592,9 +622,9 @@ def main():
         result['plain_sweeps'] = {'ms_per_step_by_seed': tps, 'aggregate_frames_per_s': round(sum(solved_of[sd] for sd in used) / (sum(tps.values()) * 1e-3), 1),
                                   'note': 'one untimed-warm step per seed with one-workgroup repair chains carried on inside the first launch'}
 
-    # ---- fixed jobs at this N (all ranks take part)
+    # ---- fixed jobs at this N (all ranks take part): the many-sequence job when it is the headline, both with --full
     strong = None
-    if not args.no_strong and args.mode == 'chunked':
+    if not args.no_strong and args.mode == 'chunked' and (args.full or headline_is_strong):
         strong = {}
         try:
             n_here, t_here, n_local, t_one, n_one, s_reps, s_warm = strong_many()
@@ -617,20 +647,21 @@ def main():
                                                                 'note': 'rank 0 alone on the whole job, same box, before the sharded run'}
         except Exception as e:
             strong['many_sequences'] = {'error': repr(e)}
-        try:
-            n_here, t_here, info, ncalls = strong_long()
-            t_job = allmax(t_here)
-            n_job = allsum(n_here)
-            strong['long_sequence'] = {
-                'workload': f'one {args.long_frames}-frame SMPL-H sequence (BASELINE config 5 shape) cut into {world} frame range(s), '
-                            f'{args.chunk_warmup}-frame warm-up overlap, hand-offs verified to {args.verify_tol:g} and repaired '
-                            '(parallel.solve_sequence_sharded); host buffers (PCIe staging inside the time)',
-                'frames': int(n_job), 'frames_per_s': round(n_job / t_job, 1), 'ms': round(t_job * 1e3, 2),
-                'handoff_repair_rounds': int(info['rounds']), 'ranks_repaired': info['repaired'],
-                'max_handoff_dev': float(info['max_handoff_dev']), 'rank0_idle_ms': round((t_job - t_here) * 1e3, 2),
-                'solves_on_rank0': ncalls}
-        except Exception as e:
-            strong['long_sequence'] = {'error': repr(e)}
+        if args.full:
+            try:
+                n_here, t_here, info, ncalls = strong_long()
+                t_job = allmax(t_here)
+                n_job = allsum(n_here)
+                strong['long_sequence'] = {
+                    'workload': f'one {args.long_frames}-frame SMPL-H sequence (BASELINE config 5 shape) cut into {world} frame range(s), '
+                                f'{args.chunk_warmup}-frame warm-up overlap, hand-offs verified to {args.verify_tol:g} and repaired '
+                                '(parallel.solve_sequence_sharded); host buffers (PCIe staging inside the time)',
+                    'frames': int(n_job), 'frames_per_s': round(n_job / t_job, 1), 'ms': round(t_job * 1e3, 2),
+                    'handoff_repair_rounds': int(info['rounds']), 'ranks_repaired': info['repaired'],
+                    'max_handoff_dev': float(info['max_handoff_dev']), 'rank0_idle_ms': round((t_job - t_here) * 1e3, 2),
+                    'solves_on_rank0': ncalls}
+            except Exception as e:
+                strong['long_sequence'] = {'error': repr(e)}
         result['strong'] = strong
         if (args.scaling == 'strong' or (args.scaling == 'auto' and world > 1)) and 'frames_per_s' in strong.get('many_sequences', {}):
             sj = strong['many_sequences']
@@ -685,7 +716,9 @@ def main():
             'dogleg_iters_per_frame': round(float(iters[solved_mask, 0].sum()) / max(solved, 1), 3),
             'residual_evals_per_frame': round(float(iters[solved_mask, 1].sum()) / max(solved, 1), 3), 'lds_bytes': lds,
         }
-        extras = world == 1     # the reference / CPU / Stage-I legs run at N = 1 only: at N > 1 the other ranks would idle at the barrier
+        # the legs beyond the headline (--full); the reference / CPU / Stage-I legs run at N = 1 only: at N > 1 the other ranks would idle
+        # at the barrier
+        extras = args.full and world == 1
         # ---- the literal frame order on one workgroup, and the timed mode's deviation from it over all frames
         if extras and args.mode == 'chunked' and not args.no_sequential:
             dsq = workload.DeviceSequence(job, solver, dev)
@@ -876,75 +909,76 @@ def main():
             pv['frames_parted_on_a_knife_edge'] += int(sum(v['frames_parted_on_a_knife_edge'] for v in goodc))
             pv['frames_over_1e-4_rad'] += int(sum(v['frames_over_1e-4_rad'] for v in goodc))
             pv['all_ok'] = bool(pv['all_ok'] and all(v['ok'] for v in goodc) and 'error' not in cfgs)
-        # ---- full-mesh LBS export kernel (the kernel the HBM-roofline target names).  Two bodies of the same sizes: the synthetic SMPL-H
-        #      with its vertices in MESH order (bone by bone, along each bone -- how a registered artist mesh numbers them: consecutive
-        #      ids share joints, which is what the kernel's per-group joint lists profit from) -- `roofline_lbs` -- and the same body
-        #      with SHUFFLED vertex ids (the worst case; what every solver fixture of this repository uses) beside it.
-        try:
-            import ctypes as C
-            from moshpp_amd import synth
-            Fl = min(args.lbs_frames, F)
-            pose32 = ds.pose[:Fl].to(torch.float32).contiguous()
-            trans32 = ds.trans[:Fl].to(torch.float32).contiguous()
-            stream = torch.cuda.current_stream().cuda_stream
+        if args.full:
+            # ---- full-mesh LBS export kernel (the kernel the HBM-roofline target names).  Two bodies of the same sizes: the synthetic SMPL-H
+            #      with its vertices in MESH order (bone by bone, along each bone -- how a registered artist mesh numbers them: consecutive
+            #      ids share joints, which is what the kernel's per-group joint lists profit from) -- `roofline_lbs` -- and the same body
+            #      with SHUFFLED vertex ids (the worst case; what every solver fixture of this repository uses) beside it.
+            try:
+                import ctypes as C
+                from moshpp_amd import synth
+                Fl = min(args.lbs_frames, F)
+                pose32 = ds.pose[:Fl].to(torch.float32).contiguous()
+                trans32 = ds.trans[:Fl].to(torch.float32).contiguous()
+                stream = torch.cuda.current_stream().cuda_stream
 
-            def lbs_leg(slv, tag, pose_t, what, pmc_tag=None):
-                smv = slv.sm if hasattr(slv, 'sm') else sm
-                verts = torch.empty((Fl, smv.V, 3), dtype=torch.float32, device=dev)
-                for _ in range(2):
-                    slv.dev.lbs_forward_device(Fl, pose_t.data_ptr(), trans32.data_ptr(), verts.data_ptr(), C.c_void_p(stream))
-                torch.cuda.synchronize()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                reps = 10
-                e0.record()
-                for _ in range(reps):
-                    slv.dev.lbs_forward_device(Fl, pose_t.data_ptr(), trans32.data_ptr(), verts.data_ptr(), C.c_void_p(stream))
-                e1.record()
-                torch.cuda.synchronize()
-                lt = e0.elapsed_time(e1) * 1e-3 / reps
-                # a 60-frame spot check of the timed output against the reference-precision kernel
-                chk = slv.dev.lbs_forward(pose_t[:60].cpu().numpy().astype(np.float64), trans32[:60].cpu().numpy().astype(np.float64))
-                err = float(np.abs(verts[:60].cpu().numpy() - chk).max())
-                Kj = smv.K
-                # algorithmic bytes as SURVEY.md section 8(d) / BASELINE.md section 4 state them: 12 V out + pose/trans in per frame, plus ONE
-                # read of the f32 model, 12 V (1 + 9 (K - 1)) + 4 V K bytes (SMPL-H: 39.5 MB; the kernel actually reads f16 posedirs -- 19 MB:
-                # `frac_with_f16_model_bytes` is the same time under rounds 3-4's accounting)
-                model_bytes = 12 * smv.V * (1 + 9 * (Kj - 1)) + 4 * smv.V * Kj
-                bytes_alg = Fl * (12 * smv.V + 4 * smv.NP + 12) + model_bytes
-                bytes_f16 = Fl * (12 * smv.V + 4 * smv.NP + 12) + 6 * smv.V * 9 * (Kj - 1) + 16 * smv.V
-                pm = pmc.get('lbs', {}).get(pmc_tag or tag) if pmc else None
-                return {'kernel': 'k_lbs_export (+ k_lbs_prep, k_lbs_still)', 'bound': 'hbm', 'body': tag, 'poses': what,
-                        'dtype': 'f32 out; f16-operand / f32-accumulate MFMA correctives, f32 blend on the f32 matrix instruction',
-                        'achieved': round(bytes_alg / lt / 1e9, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': round(bytes_alg / lt / 1e9 / HBM_PEAK_GBS, 4),
-                        'frac_with_f16_model_bytes': round(bytes_f16 / lt / 1e9 / HBM_PEAK_GBS, 4),
-                        'algorithmic_bytes': int(bytes_alg),
-                        'traffic': int(pm['bytes_per_call_at_4000_frames'] * Fl / 4000.0) if pm else None, 'traffic_is': pmc_is, 'traffic_source': pmc_note,
-                        'frames': Fl, 'kernel_ms': round(lt * 1e3, 3), 'frames_per_s': round(Fl / lt, 1),
-                        'max_abs_err_vs_f64_kernel_m_first_60_frames': err}
+                def lbs_leg(slv, tag, pose_t, what, pmc_tag=None):
+                    smv = slv.sm if hasattr(slv, 'sm') else sm
+                    verts = torch.empty((Fl, smv.V, 3), dtype=torch.float32, device=dev)
+                    for _ in range(2):
+                        slv.dev.lbs_forward_device(Fl, pose_t.data_ptr(), trans32.data_ptr(), verts.data_ptr(), C.c_void_p(stream))
+                    torch.cuda.synchronize()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    reps = 10
+                    e0.record()
+                    for _ in range(reps):
+                        slv.dev.lbs_forward_device(Fl, pose_t.data_ptr(), trans32.data_ptr(), verts.data_ptr(), C.c_void_p(stream))
+                    e1.record()
+                    torch.cuda.synchronize()
+                    lt = e0.elapsed_time(e1) * 1e-3 / reps
+                    # a 60-frame spot check of the timed output against the reference-precision kernel
+                    chk = slv.dev.lbs_forward(pose_t[:60].cpu().numpy().astype(np.float64), trans32[:60].cpu().numpy().astype(np.float64))
+                    err = float(np.abs(verts[:60].cpu().numpy() - chk).max())
+                    Kj = smv.K
+                    # algorithmic bytes as SURVEY.md section 8(d) / BASELINE.md section 4 state them: 12 V out + pose/trans in per frame, plus ONE
+                    # read of the f32 model, 12 V (1 + 9 (K - 1)) + 4 V K bytes (SMPL-H: 39.5 MB; the kernel actually reads f16 posedirs -- 19 MB:
+                    # `frac_with_f16_model_bytes` is the same time under rounds 3-4's accounting)
+                    model_bytes = 12 * smv.V * (1 + 9 * (Kj - 1)) + 4 * smv.V * Kj
+                    bytes_alg = Fl * (12 * smv.V + 4 * smv.NP + 12) + model_bytes
+                    bytes_f16 = Fl * (12 * smv.V + 4 * smv.NP + 12) + 6 * smv.V * 9 * (Kj - 1) + 16 * smv.V
+                    pm = pmc.get('lbs', {}).get(pmc_tag or tag) if pmc else None
+                    return {'kernel': 'k_lbs_export (+ k_lbs_prep, k_lbs_still)', 'bound': 'hbm', 'body': tag, 'poses': what,
+                            'dtype': 'f32 out; f16-operand / f32-accumulate MFMA correctives, f32 blend on the f32 matrix instruction',
+                            'achieved': round(bytes_alg / lt / 1e9, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': round(bytes_alg / lt / 1e9 / HBM_PEAK_GBS, 4),
+                            'frac_with_f16_model_bytes': round(bytes_f16 / lt / 1e9 / HBM_PEAK_GBS, 4),
+                            'algorithmic_bytes': int(bytes_alg),
+                            'traffic': int(pm['bytes_per_call_at_4000_frames'] * Fl / 4000.0) if pm else None, 'traffic_is': pmc_is, 'traffic_source': pmc_note,
+                            'frames': Fl, 'kernel_ms': round(lt * 1e3, 3), 'frames_per_s': round(Fl / lt, 1),
+                            'max_abs_err_vs_f64_kernel_m_first_60_frames': err}
 
-            # the poses: (a) the SOLVED sequence as it is -- a body-only solve (the reference's default, optimize_fingers off) leaves the hand
-            # pose at the prior's mean in every frame, which the export notices per call (k_lbs_prep's marks) and folds into the rest
-            # positions (k_lbs_still): 6 of SMPL-H's 15 k-steps remain; (b) the same sequence with every hand-pose variable moving
-            what_a = 'the solved config[1] sequence (body-only Stage-II: the hand pose is the same in every frame)'
-            what_b = 'the solved sequence with seeded N(0, 0.3) hand-pose variables in every frame (every joint moves)'
-            pose_mv = pose32.clone()
-            gen = torch.Generator(device='cpu'); gen.manual_seed(1234)
-            pose_mv[:, sm.body_dof:] = (0.3 * torch.randn((Fl, sm.NP - sm.body_dof), generator=gen)).to(dev)
-            dd_mesh = synth.synth_model('smplh', seed=seeds[0], vertex_order='mesh')
-            job_mesh = workload.make_job('smplh', n_frames=8, n_markers=M, seed=seeds[0], dd=dd_mesh)
-            solver_mesh = workload.make_solver(job_mesh)
-            result['roofline_lbs'] = lbs_leg(solver_mesh, 'mesh_order', pose32, what_a)
-            result['roofline_lbs']['all_joints_moving'] = lbs_leg(solver_mesh, 'mesh_order', pose_mv, what_b, 'mesh_order_moving')
-            result['roofline_lbs']['shuffled_vertex_ids'] = lbs_leg(solver, 'shuffled_ids', pose32, what_a)
-            result['roofline_lbs']['shuffled_vertex_ids_all_joints_moving'] = lbs_leg(solver, 'shuffled_ids', pose_mv, what_b, 'shuffled_ids_moving')
-            result['roofline_lbs']['limit_note'] = (
-                'round 6: the blend runs on v_mfma_f32_16x16x4_f32 (12 matrix instructions a 16-frame block and round of four joints; the packed FMAs of round 5 '
-                'could not overlap the matrix pipe at all: profiles/r06_ubench_valu.txt), still joints leave the k-loop; what remains per 64 x 128 tile and wave is '
-                '~6 k-steps x 24 + 96 f32 matrix instructions + ~80 vector / LDS / memory instructions a block, issue-bound at two waves per SIMD, plus ~25 us of '
-                'k_lbs_prep + k_lbs_still + kernel boundaries per call (DESIGN.md section 6)')
-            del solver_mesh
-        except Exception as e:   # the LBS leg must never take the headline number down
-            result['roofline_lbs'] = {'error': repr(e)}
+                # the poses: (a) the SOLVED sequence as it is -- a body-only solve (the reference's default, optimize_fingers off) leaves the hand
+                # pose at the prior's mean in every frame, which the export notices per call (k_lbs_prep's marks) and folds into the rest
+                # positions (k_lbs_still): 6 of SMPL-H's 15 k-steps remain; (b) the same sequence with every hand-pose variable moving
+                what_a = 'the solved config[1] sequence (body-only Stage-II: the hand pose is the same in every frame)'
+                what_b = 'the solved sequence with seeded N(0, 0.3) hand-pose variables in every frame (every joint moves)'
+                pose_mv = pose32.clone()
+                gen = torch.Generator(device='cpu'); gen.manual_seed(1234)
+                pose_mv[:, sm.body_dof:] = (0.3 * torch.randn((Fl, sm.NP - sm.body_dof), generator=gen)).to(dev)
+                dd_mesh = synth.synth_model('smplh', seed=seeds[0], vertex_order='mesh')
+                job_mesh = workload.make_job('smplh', n_frames=8, n_markers=M, seed=seeds[0], dd=dd_mesh)
+                solver_mesh = workload.make_solver(job_mesh)
+                result['roofline_lbs'] = lbs_leg(solver_mesh, 'mesh_order', pose32, what_a)
+                result['roofline_lbs']['all_joints_moving'] = lbs_leg(solver_mesh, 'mesh_order', pose_mv, what_b, 'mesh_order_moving')
+                result['roofline_lbs']['shuffled_vertex_ids'] = lbs_leg(solver, 'shuffled_ids', pose32, what_a)
+                result['roofline_lbs']['shuffled_vertex_ids_all_joints_moving'] = lbs_leg(solver, 'shuffled_ids', pose_mv, what_b, 'shuffled_ids_moving')
+                result['roofline_lbs']['limit_note'] = (
+                    'round 6: the blend runs on v_mfma_f32_16x16x4_f32 (12 matrix instructions a 16-frame block and round of four joints; the packed FMAs of round 5 '
+                    'could not overlap the matrix pipe at all: profiles/r06_ubench_valu.txt), still joints leave the k-loop; what remains per 64 x 128 tile and wave is '
+                    '~6 k-steps x 24 + 96 f32 matrix instructions + ~80 vector / LDS / memory instructions a block, issue-bound at two waves per SIMD, plus ~25 us of '
+                    'k_lbs_prep + k_lbs_still + kernel boundaries per call (DESIGN.md section 6)')
+                del solver_mesh
+            except Exception as e:   # the LBS leg must never take the headline number down
+                result['roofline_lbs'] = {'error': repr(e)}
         # ---- CPU baseline: the NumPy oracle ("port") on bounded samples of the same workload; parity on the first sample
         if extras and not args.no_cpu:
             from oracle import stageii_oracle as so
@@ -1070,6 +1104,9 @@ def main():
                 result['stagei'] = leg
             except Exception as e:
                 result['stagei'] = {'error': repr(e)}
+        t_end = time.perf_counter()
+        result['wall_seconds'] = {'setup': round(t_ready - t_start, 2), 'warmup': round(t_steps_end - t_local - t_ready, 2), 'timed': round(t_local, 2),
+                                  'after_the_steps': round(t_end - t_steps_end, 2), 'total_in_main': round(t_end - t_start, 2)}
         result = _finite(result)
         result['detail_file'] = write_detail(result) or 'stderr only'
         line = compact_line(result)

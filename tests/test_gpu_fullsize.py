@@ -435,7 +435,7 @@ def test_underdetermined_frames_on_the_device(gpu_lib):
 
 @pytest.mark.gpu
 def test_bench_launches_its_own_ranks(gpu_lib):
-    """`python bench.py --gpus 2` without a launcher starts two ranks itself (torch.distributed.run on 127.0.0.1) and reports
+    """`python bench.py --gpus 2 --full` without a launcher starts two ranks itself (torch.distributed.run on 127.0.0.1) and reports
     n_gpus = 2.  MOSHII_BENCH_ONE_GPU=1 puts both ranks on cuda:0 with gloo (one GPU per box here), so the N > 1 code paths of the
     bench -- partition of the fixed jobs, sharded long sequence, max-over-ranks timing -- run; the numbers mean nothing."""
     import json
@@ -446,7 +446,7 @@ def test_bench_launches_its_own_ranks(gpu_lib):
     env = dict(os.environ, MOSHII_BENCH_ONE_GPU='1')
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--frames', '600',
+    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--gpus', '2', '--steps', '2', '--warmup', '1', '--frames', '600',
                         '--seeds', '1000,123', '--no-cpu', '--no-stagei', '--no-sequential', '--strong-sequences', '4', '--long-frames', '1500',
                         '--lbs-frames', '200', '--no-config3'], capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -455,6 +455,39 @@ def test_bench_launches_its_own_ranks(gpu_lib):
     res = json.loads(lines[0])
     assert res['n_gpus'] == 2 and res['value'] > 0
     assert res['strong']['many_sequences']['frames'] == 4 * 600
+    assert res['strong']['long_sequence']['frames'] > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('gpus', [1, 2])
+def test_a_plain_bench_run_measures_the_headline_alone(gpu_lib, gpus):
+    """Without --full, bench.py sets up, warms up, times its steps and prints the line: no leg that takes runs of its own is measured.
+    At N > 1 (both ranks on cuda:0, as above) the headline is the fixed many-sequence job, and that job alone runs."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, MOSHII_BENCH_ONE_GPU='1')
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
+        env.pop(k, None)
+    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(gpus), '--steps', '2', '--warmup', '1', '--frames', '600',
+                        '--seeds', '1000,123', '--strong-sequences', '4'], capture_output=True, text=True, timeout=900, env=env, cwd=root)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, p.stdout[-2000:]
+    res = json.loads(lines[0])
+    detail = json.loads([l for l in p.stderr.splitlines() if l.startswith('bench detail: ')][-1][len('bench detail: '):])
+    assert res['n_gpus'] == gpus and res['value'] > 0 and res['ms_per_step'] > 0 and res['dtype'] == 'f64'
+    assert res['roofline']['kernel'] and res['roofline']['frac'] > 0
+    for leg in ('plain_sweeps', 'sequential_chain', 'parity', 'parity_every_frame', 'incl_host_staging', 'many_sequences', 'config3',
+                'roofline_lbs', 'cpu_baseline', 'stagei', 'one_gpu_same_job'):
+        assert leg not in detail, leg
+    if gpus == 1:
+        assert res['scaling'] == 'weak' and res['steps'] == 2 and res['warmup'] == 1 and 'strong' not in detail
+    else:
+        assert res['scaling'] == 'strong' and res['steps'] == 2 and res['warmup'] == 1
+        assert set(detail['strong']) == {'many_sequences'} and res['strong']['many_sequences']['frames'] == 4 * 600
 
 
 @pytest.mark.gpu

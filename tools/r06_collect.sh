@@ -6,8 +6,9 @@
 # Output under gpurun_out/r06/; copy the summaries to profiles/.
 cd /root/repo; export TMPDIR=/tmp PYTHONPATH=/root/repo
 O=gpurun_out/r06; mkdir -p $O
+R=$PWD
 ( hostname; date +%T ) > $O/box_probe.txt 2>&1
-(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /root/repo/$O/stats -o bench -- python /root/repo/bench.py --no-cpu --no-stagei --no-config3 > /root/repo/$O/bench_line_under_rocprof.json 2> /root/repo/$O/rocprof_err.txt)
+(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/stats" -o bench -- python "$R/bench.py" --full --no-cpu --no-stagei --no-config3 > "$R/$O/bench_line_under_rocprof.json" 2> "$R/$O/rocprof_err.txt")
 cp $O/stats/bench_kernel_stats.csv $O/ 2>/dev/null
 python - <<'PY' > $O/bench_launches.txt 2>&1
 import csv, glob
@@ -15,7 +16,7 @@ rows = []
 for fn in glob.glob('gpurun_out/r06/stats/*kernel_trace.csv'):
     rows += list(csv.DictReader(open(fn)))
 rows.sort(key=lambda r: int(r['Start_Timestamp']))
-print('# k_chain_solve / k_lbs launches of `python bench.py --no-cpu --no-stagei --no-config3` in dispatch order: duration (ms), grid, scratch B/lane, VGPR, AGPR, LDS')
+print('# k_chain_solve / k_lbs launches of `python bench.py --full --no-cpu --no-stagei --no-config3` in dispatch order: duration (ms), grid, scratch B/lane, VGPR, AGPR, LDS')
 for r in rows:
     n = r['Kernel_Name']
     if 'k_chain_solve' in n or 'k_lbs' in n:
@@ -57,7 +58,7 @@ done
 } > $O/lbs_sq_counters.txt
 # ---- memory-side PMC passes
 for c in FETCH_SIZE WRITE_SIZE; do
-  (cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d /root/repo/$O/pmc_chain_$c -- python /root/repo/bench.py --no-cpu --no-stagei --no-strong --no-config3 --no-sequential --steps 1 --warmup 1 --seeds 1000 > /dev/null 2> /root/repo/$O/pmc_chain_${c}_err.txt)
+  (cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d "$R/$O/pmc_chain_$c" -- python "$R/bench.py" --full --no-cpu --no-stagei --no-strong --no-config3 --no-sequential --steps 1 --warmup 1 --seeds 1000 > /dev/null 2> "$R/$O/pmc_chain_${c}_err.txt")
   for body in mesh shuffled; do for hands in still moving; do
     (cd /tmp && LBS_HANDS=$hands LBS_BODY=$body timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d /root/repo/$O/pmc_lbs_${body}_${hands}_$c -- python /root/repo/tools/lbs_bench.py 4000 4 smplh > /dev/null 2> /root/repo/$O/pmc_lbs_${c}_err.txt)
   done; done
@@ -98,7 +99,7 @@ if 'FETCH_SIZE' in ch and 'WRITE_SIZE' in ch:
     out['chain'] = {'pass1_bytes_per_solved_frame': (2 * ch['FETCH_SIZE']['pass1'] + ch['WRITE_SIZE']['pass1']) / frames_pass1,
                     'repair_bytes_per_step': 2 * ch['FETCH_SIZE']['repair'] + ch['WRITE_SIZE']['repair'],
                     'pass1_fetch_size_reported': ch['FETCH_SIZE']['pass1'], 'pass1_write_size': ch['WRITE_SIZE']['pass1'],
-                    'frames_solved_in_pass1': frames_pass1, 'command': 'bench.py --no-cpu --no-stagei --no-strong --no-config3 --no-sequential --steps 1 --warmup 1 --seeds 1000'}
+                    'frames_solved_in_pass1': frames_pass1, 'command': 'bench.py --full --no-cpu --no-stagei --no-strong --no-config3 --no-sequential --steps 1 --warmup 1 --seeds 1000'}
 lbs = {}
 for body, btag in (('mesh', 'mesh_order'), ('shuffled', 'shuffled_ids')):
     for hands, htag in (('still', ''), ('moving', '_moving')):
@@ -128,6 +129,6 @@ rm -rf $O/pmc_chain_* $O/pmc_lbs_*
 rm -rf $O/s1prof $O/stagei_time.txt
 # ---- the bench line LAST, with the counters just collected on this very build in place
 cp $O/r06_pmc.json profiles/r06_pmc.json
-timeout 1800 python bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_err.txt
+timeout 1800 python bench.py --full --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_err.txt
 cp bench_detail.json $O/bench_detail.json 2>/dev/null
 ls $O

@@ -138,6 +138,19 @@ int moshii_lbs_forward_f64(moshii_model_t m, int32_t F, const double* pose, cons
 int moshii_lbs_forward_f32(moshii_model_t m, int32_t F, const float* pose, const float* trans,
                            float* verts, uint32_t flags, void* stream);
 
+/* The same exports with per-frame coefficients of the free shape block (version 103): shape[F][nshape], nshape = the count
+ * declared by moshii_model_set_free_shape -- the `expression` / `dmpls` a Stage-II solve returns, as an OFFSET on the frozen
+ * betas exactly as in the chain solve:  v_shaped_f = v_shaped + S_free . shape[f],  J_f = J + JS . shape[f]  (rest positions AND
+ * joints move).  shape == NULL (or no block declared) is the call above, launch for launch; a non-null shape without a declared
+ * block is MOSHII_ERR_ARG.  shape lives where pose / trans / verts live (flags).
+ * _f32: the block's columns join the f16 matrix contraction in front of the pose features, every coefficient as three columns
+ *       (direction hi x coefficient hi, hi x lo, lo x hi: f16 pairs, f32 accumulate) with a power-of-two scale of their own;
+ *       the joints are moved in f32 ahead of the kinematic chain.  Same bound: |error| <= 2e-5 m against _f64. */
+int moshii_lbs_forward_shape_f64(moshii_model_t m, int32_t F, const double* pose, const double* trans, const double* shape,
+                                 double* verts, uint32_t flags, void* stream);
+int moshii_lbs_forward_shape_f32(moshii_model_t m, int32_t F, const float* pose, const float* trans, const float* shape,
+                                 float* verts, uint32_t flags, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Pose prior.  Replaces create_gmm_body_prior / MaxMixtureComplete
  * (src/moshpp/prior/gmm_prior_ch.py:42-134).  The caller passes the already prepared arrays:

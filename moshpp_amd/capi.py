@@ -88,6 +88,8 @@ EXPORTS = {
     'moshii_model_get_joints': (C.c_int, [C.c_void_p, _c_double_p]),
     'moshii_lbs_forward_f64': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     'moshii_lbs_forward_f32': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    'moshii_lbs_forward_shape_f64': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    'moshii_lbs_forward_shape_f32': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     'moshii_prior_create': (C.c_int, [C.c_int32, C.c_int32, _c_double_p, _c_double_p, _c_double_p, C.POINTER(C.c_void_p)]),
     'moshii_prior_destroy': (C.c_int, [C.c_void_p]),
     'moshii_attach_create': (C.c_int, [C.c_void_p, C.c_int32, _c_int_p, _c_double_p, C.POINTER(C.c_void_p)]),
@@ -210,20 +212,54 @@ class Model:
         check(load().moshii_model_get_joints(self.handle, _dp(out)))
         return out
 
-    def lbs_forward(self, pose, trans, dtype=np.float64):
-        """verts[F,V,3] for pose variables pose[F,NP], trans[F,3] (host arrays)."""
+    def lbs_forward(self, pose, trans, dtype=np.float64, shape=None):
+        """verts[F,V,3] for pose variables pose[F,NP], trans[F,3] (host arrays).  shape[F, nshape]: per-frame coefficients of the
+        block declared with set_free_shape (the `shape` a Stage-II solve returns: expression / DMPL offsets on the frozen betas);
+        rest positions and joints follow them."""
+        if dtype not in (np.float64, np.float32):
+            raise ValueError(f'lbs_forward: dtype must be numpy float64 or float32, not {dtype!r}')
         pose = np.ascontiguousarray(np.atleast_2d(pose), dtype=dtype)
         trans = np.ascontiguousarray(np.atleast_2d(trans), dtype=dtype)
         F = pose.shape[0]
         assert pose.shape == (F, self.NP) and trans.shape == (F, 3)
+        if shape is not None:
+            shape = self._check_shape_rows(shape, F, dtype)
         out = np.zeros((F, self.V, 3), dtype=dtype)
-        fn = load().moshii_lbs_forward_f64 if dtype == np.float64 else load().moshii_lbs_forward_f32
-        check(fn(self.handle, F, pose.ctypes.data, trans.ctypes.data, out.ctypes.data, BUFFERS_HOST, None))
+        if shape is None:
+            fn = load().moshii_lbs_forward_f64 if dtype == np.float64 else load().moshii_lbs_forward_f32
+            check(fn(self.handle, F, pose.ctypes.data, trans.ctypes.data, out.ctypes.data, BUFFERS_HOST, None))
+        else:
+            fn = load().moshii_lbs_forward_shape_f64 if dtype == np.float64 else load().moshii_lbs_forward_shape_f32
+            check(fn(self.handle, F, pose.ctypes.data, trans.ctypes.data, shape.ctypes.data, out.ctypes.data, BUFFERS_HOST, None))
         return out
 
-    def lbs_forward_device(self, F, pose_ptr, trans_ptr, out_ptr, stream=None, f32=True):
-        fn = load().moshii_lbs_forward_f32 if f32 else load().moshii_lbs_forward_f64
-        check(fn(self.handle, F, pose_ptr, trans_ptr, out_ptr, BUFFERS_DEVICE, stream))
+    def _check_shape_rows(self, shape, F, dtype):
+        """shape[F, nshape] as a contiguous array of `dtype`; ValueError (before any device call) if it cannot be that."""
+        n = int(getattr(self, 'n_free_shape', 0))
+        if n <= 0:
+            raise ValueError('lbs_forward: shape coefficients given, but the model has no free shape block (set_free_shape)')
+        shape = np.asarray(shape)
+        if shape.ndim == 1 and F == 1:
+            shape = shape[None]
+        if shape.ndim != 2 or shape.shape != (F, n):
+            raise ValueError(f'lbs_forward: shape must be [F, nshape] = [{F}, {n}], got {tuple(shape.shape)}')
+        if not np.issubdtype(shape.dtype, np.number) or np.iscomplexobj(shape):
+            raise ValueError(f'lbs_forward: shape must be real numbers, got dtype {shape.dtype}')
+        shape = np.ascontiguousarray(shape, dtype=dtype)
+        if not np.isfinite(shape).all():
+            raise ValueError('lbs_forward: shape holds non-finite coefficients')
+        return shape
+
+    def lbs_forward_device(self, F, pose_ptr, trans_ptr, out_ptr, stream=None, f32=True, shape_ptr=None):
+        """Device buffers (f32: float, else double).  shape_ptr: [F][nshape] coefficients of the free shape block on the device."""
+        if shape_ptr is None:
+            fn = load().moshii_lbs_forward_f32 if f32 else load().moshii_lbs_forward_f64
+            check(fn(self.handle, F, pose_ptr, trans_ptr, out_ptr, BUFFERS_DEVICE, stream))
+        else:
+            if int(getattr(self, 'n_free_shape', 0)) <= 0:
+                raise ValueError('lbs_forward_device: shape_ptr given, but the model has no free shape block (set_free_shape)')
+            fn = load().moshii_lbs_forward_shape_f32 if f32 else load().moshii_lbs_forward_shape_f64
+            check(fn(self.handle, F, pose_ptr, trans_ptr, shape_ptr, out_ptr, BUFFERS_DEVICE, stream))
 
     def close(self):
         if getattr(self, 'handle', None) is not None and self.handle.value:

@@ -223,6 +223,16 @@ class StageIISolver:
             return out
         raise ValueError(f'unknown chain_mode {chain_mode}')
 
+    def vertices(self, out, dtype=np.float32):
+        """verts[F, V, 3] of a solve() result: the full mesh the solved frames describe, on the solver's own model handle.  With a free
+        block (optimize_face / optimize_dynamics) the per-frame coefficients out['shape'] move rest positions and joints exactly as in
+        the solve, so the mesh carries the markers_sim the solver returned.  float32: the batched export kernels, float64: the
+        reference-precision kernel.  Rows of unsolved frames (status 1) hold whatever pose the chain carried there."""
+        for k in ('pose', 'trans') + (('shape',) if self.n_shape else ()):
+            if k not in out:
+                raise KeyError(f"StageIISolver.vertices: the result has no '{k}'")
+        return self.dev.lbs_forward(out['pose'], out['trans'], dtype=dtype, shape=out['shape'] if self.n_shape else None)
+
 
 def mosh_stageii(mocap_fname: str, cfg, markers_latent: np.ndarray, latent_labels: list, betas: np.ndarray,
                  marker_meta: dict, v_template_fname=None) -> dict:

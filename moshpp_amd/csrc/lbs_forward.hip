@@ -20,6 +20,14 @@
 //
 // Accuracy: f16 operands give |err| ~ 2^-11 |posedirs| |R - I| sqrt(9(K-1)) ~ 5e-6 m for millimetre-scale correctives
 // (tests bound it at 2e-5 m); moshii_lbs_forward_f64 is the reference-precision path.
+//
+// Free shape block (moshii_lbs_forward_shape_f32: per-frame expression / DMPL coefficients c_f, template parameter SH of the three
+// kernels; SH = false is the code without): v_posed gains S_free . c_f as KSX = ceil(3 nshape / 32) k-steps IN FRONT of the pose
+// k-steps -- every coefficient three columns, d_hi c_hi + d_hi c_lo + d_lo c_hi with (hi, lo) f16 pairs of direction and coefficient and a
+// power-of-two scale of their own (directions x pscale / sxscale, largest at 2^7 .. 2^8; coefficients x sxscale) -- and k_lbs_prep
+// moves the joints, J_f = J + JS . c_f in f32, ahead of the chain.  Measured on the MI355X against the oracle, every vertex of every
+// frame: 6.1e-6 m (SMPL-X, 80 coefficients), 6.7e-6 m (SMPL-H, 8), 3.8e-6 m (SMPL, 125) -- the pose features' error, as without a
+// block; SMPL-X with 80 coefficients 386 us per 4000-frame export against 303 us without (profiles/lbs_shape_export.txt).
 #include "../../include/moshii.h"
 #include "moshii_dev.h"
 
@@ -43,6 +51,7 @@ const double* moshii_internal_posedirs(moshii_model_t m);
 const double* moshii_internal_weights(moshii_model_t m);
 const double* moshii_internal_J(moshii_model_t m);
 const double* moshii_internal_weights_host(moshii_model_t m);
+const double* moshii_internal_shape_block(moshii_model_t m, int* NB, int* start, int* count, const double** JS);
 void* moshii_internal_l32(moshii_model_t m);
 void moshii_internal_l32_set_valid(moshii_model_t m, int v);
 }
@@ -104,6 +113,65 @@ __global__ void k_pack_pfrag(int nfeat, int KS, int ng, double pscale, const int
     }
 }
 
+// ---- free shape block (moshii_lbs_forward_shape_f32) ----
+// The block's fragments IN FRONT of the pose fragments: record (group, i, ks) of PfragX, KST = KSX + KS k-steps a row.  k-steps
+// ks < KSX hold the shape columns q = 32 ks + 8 (l >> 4) + e: coefficient q / 3, part q % 3 -- parts 0 and 1 the f16 HIGH half of
+// shapedirs[v][i][start + q / 3] * scale (against the coefficient's high and low half), part 2 the LOW half (the residual of the
+// high one, against the coefficient's high half); scale = pscale / sxscale.  k-steps behind them: a copy of Pfrag's.
+__global__ void k_pack_pfrag_shape(int NB, int start, int E, int KSX, int KS, int ng, double scale, const int* __restrict__ perm,
+                                   const double* __restrict__ sd, const _Float16* __restrict__ pfrag, _Float16* __restrict__ dst) {
+    const int KST = KSX + KS;
+    const size_t total = (size_t)ng * 3 * KST * 64 * 8;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        const int e = (int)(idx & 7);
+        const int l = (int)((idx >> 3) & 63);
+        size_t r = idx >> 9;
+        const int ks = (int)(r % KST); r /= KST;
+        const int i = (int)(r % 3);
+        const int g = (int)(r / 3);
+        if (ks >= KSX) { dst[idx] = pfrag[((((size_t)g * 3 + i) * KS + (ks - KSX)) * 64 + l) * 8 + e]; continue; }
+        const int v = perm[g * 16 + (l & 15)];
+        const int q = ks * 32 + (l >> 4) * 8 + e, c = q / 3, part = q - 3 * c;
+        _Float16 val = (_Float16)0.0f;
+        if (v >= 0 && c < E) {
+            const double d = sd[((size_t)v * 3 + i) * NB + start + c] * scale;
+            const _Float16 hi = (_Float16)d;
+            val = part < 2 ? hi : (_Float16)(d - (double)hi);
+        }
+        dst[idx] = val;
+    }
+}
+
+// JSf[(k E + e)][4] = {JS[k][e][0..2], 0} (f32): one 16-byte load per (joint, coefficient) in k_lbs_prep
+__global__ void k_cvt_js(int n, const double* __restrict__ JS, float* __restrict__ dst) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    for (int c = 0; c < 3; ++c) dst[i * 4 + c] = (float)JS[(size_t)i * 3 + c];
+    dst[i * 4 + 3] = 0.0f;
+}
+
+// Sft[(e*3 + i)*Vp + v] = shapedirs[v][i][start + e]  (plain kernel)
+__global__ void k_cvt_shapedirs(int V, int Vp, int NB, int start, int E, const double* __restrict__ sd, float* __restrict__ dst) {
+    const size_t total = (size_t)E * 3 * Vp;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        const int v = (int)(idx % Vp);
+        const int ei = (int)(idx / Vp);
+        dst[idx] = (v < V) ? (float)sd[((size_t)v * 3 + ei % 3) * NB + start + ei / 3] : 0.0f;
+    }
+}
+
+// max |shapedirs[:, :, start : start + E]|
+__global__ void k_absmax_block(size_t rows, int NB, int start, int E, const double* __restrict__ src, double* __restrict__ out) {
+    __shared__ double red[256];
+    double m = 0.0;
+    const size_t n = rows * (size_t)E;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) m = fmax(m, fabs(src[(i / E) * NB + start + i % E]));
+    red[threadIdx.x] = m;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + o]); __syncthreads(); }
+    if (threadIdx.x == 0) out[blockIdx.x] = red[0];
+}
+
 // rest positions in group order, x pscale: vshs[slot] = {x, y, z, 0} of vertex perm[slot]
 __global__ void k_pack_vsh(int n, float pscale, const int* __restrict__ perm, const double* __restrict__ vsh, float* __restrict__ dst) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -114,15 +182,25 @@ __global__ void k_pack_vsh(int n, float pscale, const int* __restrict__ perm, co
 }
 
 // ---- fallback kernel: one workgroup = 256 vertices of one frame (plain f32, dense weights) ----------------
+// shape: rows of free-shape coefficients [F][lm.nshape], or null -- the frame's joints then move by JS . shape[f] (LDS copy Jf), its
+// rest positions by the block's directions
 __global__ __launch_bounds__(256) void k_lbs_f32_v0(ModelDev md, Lbs32Model lm, const float* __restrict__ pose,
-                                                     const float* __restrict__ trans, float* __restrict__ out) {
+                                                     const float* __restrict__ trans, const float* __restrict__ shape, float* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) float smf[];
     const int K = md.K, P = md.P;
     float* fullpose = smf;            // P
     float* Rl = fullpose + P;         // K*9
     float* A = Rl + K * 9;            // K*12 : [Rw | tw - Rw J]
     float* feat = A + K * 12;         // K*9
+    float* Jf = feat + K * 9;         // K*3: this frame's joints
     const int f = blockIdx.y, tid = threadIdx.x;
+    const int E = shape != nullptr ? lm.nshape : 0;
+    const float* cf = shape != nullptr ? shape + (size_t)f * E : nullptr;
+    for (int d = tid; d < K * 3; d += blockDim.x) {
+        float s = lm.J[d];
+        for (int e = 0; e < E; ++e) s = fmaf(lm.JSf[((size_t)(d / 3) * E + e) * 4 + d % 3], cf[e], s);
+        Jf[d] = s;
+    }
     const float* ps = pose + (size_t)f * md.NP;
     for (int d = tid; d < P; d += blockDim.x) {
         float v;
@@ -155,20 +233,20 @@ __global__ __launch_bounds__(256) void k_lbs_f32_v0(ModelDev md, Lbs32Model lm, 
     if (tid == 0) {
         float Rw[MOSHII_MAXK * 9], tw[MOSHII_MAXK * 3];
         for (int e = 0; e < 9; ++e) Rw[e] = Rl[e];
-        for (int i = 0; i < 3; ++i) tw[i] = lm.J[i];
+        for (int i = 0; i < 3; ++i) tw[i] = Jf[i];
         for (int k = 1; k < K; ++k) {
             const int p = md.parents[k];
             for (int i = 0; i < 3; ++i) {
                 for (int j = 0; j < 3; ++j)
                     Rw[k * 9 + i * 3 + j] = Rw[p * 9 + i * 3 + 0] * Rl[k * 9 + j] + Rw[p * 9 + i * 3 + 1] * Rl[k * 9 + 3 + j] + Rw[p * 9 + i * 3 + 2] * Rl[k * 9 + 6 + j];
-                tw[k * 3 + i] = Rw[p * 9 + i * 3 + 0] * (lm.J[k * 3 + 0] - lm.J[p * 3 + 0]) + Rw[p * 9 + i * 3 + 1] * (lm.J[k * 3 + 1] - lm.J[p * 3 + 1]) +
-                                Rw[p * 9 + i * 3 + 2] * (lm.J[k * 3 + 2] - lm.J[p * 3 + 2]) + tw[p * 3 + i];
+                tw[k * 3 + i] = Rw[p * 9 + i * 3 + 0] * (Jf[k * 3 + 0] - Jf[p * 3 + 0]) + Rw[p * 9 + i * 3 + 1] * (Jf[k * 3 + 1] - Jf[p * 3 + 1]) +
+                                Rw[p * 9 + i * 3 + 2] * (Jf[k * 3 + 2] - Jf[p * 3 + 2]) + tw[p * 3 + i];
             }
         }
         for (int k = 0; k < K; ++k)
             for (int i = 0; i < 3; ++i) {
                 for (int j = 0; j < 3; ++j) A[k * 12 + i * 4 + j] = Rw[k * 9 + i * 3 + j];
-                A[k * 12 + i * 4 + 3] = tw[k * 3 + i] - (Rw[k * 9 + i * 3 + 0] * lm.J[k * 3 + 0] + Rw[k * 9 + i * 3 + 1] * lm.J[k * 3 + 1] + Rw[k * 9 + i * 3 + 2] * lm.J[k * 3 + 2]);
+                A[k * 12 + i * 4 + 3] = tw[k * 3 + i] - (Rw[k * 9 + i * 3 + 0] * Jf[k * 3 + 0] + Rw[k * 9 + i * 3 + 1] * Jf[k * 3 + 1] + Rw[k * 9 + i * 3 + 2] * Jf[k * 3 + 2]);
             }
     }
     __syncthreads();
@@ -180,6 +258,11 @@ __global__ __launch_bounds__(256) void k_lbs_f32_v0(ModelDev md, Lbs32Model lm, 
         const float fq = feat[9 + q];
         const float* pq = lm.posedirs_t + (size_t)q * 3 * Vp + v;
         vp[0] += pq[0] * fq; vp[1] += pq[Vp] * fq; vp[2] += pq[2 * Vp] * fq;
+    }
+    for (int e = 0; e < E; ++e) {
+        const float ce = cf[e];
+        const float* sq = lm.Sft + (size_t)e * 3 * Vp + v;
+        vp[0] += sq[0] * ce; vp[1] += sq[Vp] * ce; vp[2] += sq[2 * Vp] * ce;
     }
     float T[12];
     for (int e = 0; e < 12; ++e) T[e] = 0.0f;
@@ -249,13 +332,22 @@ __global__ void k_pack_jtab(ModelDev md, const float* __restrict__ Jf, const flo
 #ifndef LBS_PREP_WAVES
 #define LBS_PREP_WAVES 16      // frames (= waves) per workgroup of k_lbs_prep: a whole 16-frame block
 #endif
+// SH: the frame carries E coefficients of the free shape block (shape[F][E]).  They become its first KSX k-steps of features -- coefficient e
+// as the f16 pair (hi, lo) of c_e x sxscale in the columns 3e (hi), 3e + 1 (lo), 3e + 2 (hi), matching k_pack_pfrag_shape; KS counts
+// ALL k-steps then, the pose features start at column 32 KSX -- and move the joints, J_f = J + JS . c_f in f32, ahead of the chain
+// (lane j: E 16-byte loads of JSf, the coefficients fetched across lanes; the parent's joint across lanes too).
+#define LBS_PREP_KSMAX 28      // k-steps of a feature row with a block: 16 (pose, K <= 57) + 12 (3 x 125 shape columns)
+template <bool SH>
 __global__ __launch_bounds__(64 * LBS_PREP_WAVES, LBS_PREP_WAVES == 16 ? 1 : 4) void k_lbs_prep(ModelDev md, const float* __restrict__ jtab, const float* __restrict__ hcj, const float* __restrict__ hcompf,
                                                    int F, int KS, int KJ,
                                                    const float* __restrict__ pose, const float* __restrict__ trans,
                                                    float* __restrict__ Atr, _Float16* __restrict__ featF, int* __restrict__ varflag, int epoch,
-                                                   long long* __restrict__ stamps) {
+                                                   long long* __restrict__ stamps,
+                                                   const float* __restrict__ JSf, const float* __restrict__ shape, int E, int KSX, float sxscale) {
 #define PREP_STAMP(K) { if (stamps != nullptr && blockIdx.x == 0 && threadIdx.x == 0) stamps[K] = clock64(); }
-    __shared__ __attribute__((aligned(16))) _Float16 s_feat[LBS_PREP_WAVES][16 * 32];   // the workgroup's frames' feature rows (KS <= 16 k-steps of 32), zero padded
+    constexpr int NFE = (SH ? LBS_PREP_KSMAX : 16) * 32;
+    __shared__ __attribute__((aligned(16))) _Float16 s_feat[LBS_PREP_WAVES][NFE];   // the workgroup's frames' feature rows (KS <= 16 k-steps of 32; with a block <= 28), zero padded
+    const int fpose = SH ? KSX * 32 : 0;         // column of the first pose feature
     const int K = md.K, wv = threadIdx.x >> 6, tid = threadIdx.x & 63;
     // Workgroup -> frames: a workgroup is 16 waves = one whole 16-frame block of the outputs (768-byte runs of a joint's transforms, 1 KB
     // feature records), completed by one CU in one L2 and leaving it as whole lines.  (What bounds the kernel is the instruction count:
@@ -270,7 +362,7 @@ __global__ __launch_bounds__(64 * LBS_PREP_WAVES, LBS_PREP_WAVES == 16 ? 1 : 4) 
     const int fw = fbase + wv;                   // this wave's frame; spare waves behind the last frame redo frame F - 1 and write nothing
     const int f = __builtin_amdgcn_readfirstlane(min(fw, F - 1));
     PREP_STAMP(0)
-    for (int q = tid; q < 16 * 32; q += 64) s_feat[wv][q] = (_Float16)0.0f;
+    for (int q = tid; q < NFE; q += 64) s_feat[wv][q] = (_Float16)0.0f;
     // (no instruction on the device, where a wave's lanes move together; the CPU emulation runs them one after another and meets here:
     //  the features written below must not be zeroed by a lane that comes later)
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -292,6 +384,11 @@ __global__ __launch_bounds__(64 * LBS_PREP_WAVES, LBS_PREP_WAVES == 16 ? 1 : 4) 
     for (int i = 0; i < 3; ++i) { bv[i] = psb[cb + i]; b0[i] = p0b[cb + i]; }
     const int hl = bd + min(tid, max(hd - 1, 0));
     const unsigned phb = hd > 0 ? psb[hl] : 0u, ph0 = hd > 0 ? p0b[hl] : 0u;
+    float cr0 = 0.0f, cr1 = 0.0f;                // (SH) lane i: coefficients i and 64 + i of this frame (E <= 128)
+    if (SH) {
+        const float* cf = shape + (size_t)f * E;
+        cr0 = cf[min(tid, E - 1)]; cr1 = cf[min(tid + 64, E - 1)];
+    }
     // (the elements are copied to scalars first: __builtin_bit_cast applied to a vector ELEMENT expression read element 0 in the host build)
     const float q0x = q0.x, q0z = q0.z, q0w = q0.w, q3w = q3.w;
     const bool hand = __builtin_bit_cast(int, q3w) != 0;
@@ -304,7 +401,32 @@ __global__ __launch_bounds__(64 * LBS_PREP_WAVES, LBS_PREP_WAVES == 16 ? 1 : 4) 
         for (int u = 0; u < 16; ++u) cv[u] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     }
     const int p = __builtin_bit_cast(int, q0x), i0 = __builtin_bit_cast(int, q0z), i1 = __builtin_bit_cast(int, q0w);
-    const float Jme[3] = {q1.x, q1.y, q1.z}, Jd[3] = {q2.x, q2.y, q2.z};
+    float Jme[3] = {q1.x, q1.y, q1.z}, Jd[3] = {q2.x, q2.y, q2.z};
+    if (SH) {   // this frame's joints: J_j + sum_e c_e JS[j][e]; the offset to the parent from the parent's lane
+        const f32x4* js = reinterpret_cast<const f32x4*>(JSf) + (size_t)j * E;
+        for (int e = 0; e < E; ++e) {
+            const float ce = __shfl(e < 64 ? cr0 : cr1, e & 63);
+            const f32x4 d = js[e];
+            Jme[0] = fmaf(ce, d.x, Jme[0]); Jme[1] = fmaf(ce, d.y, Jme[1]); Jme[2] = fmaf(ce, d.z, Jme[2]);
+        }
+        const int psrc = max(p, 0);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const float jp = __shfl(Jme[i], psrc);
+            Jd[i] = p >= 0 ? Jme[i] - jp : Jme[i];
+        }
+        // the coefficients as features: c x sxscale = hi + lo in f16 (clamped far inside the f16 range)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int e = tid + 64 * h;
+            if (e < E) {
+                const float c = fminf(fmaxf((h == 0 ? cr0 : cr1) * sxscale, -32768.0f), 32768.0f);
+                const _Float16 chi = (_Float16)c;
+                const _Float16 clo = (_Float16)(c - (float)chi);
+                s_feat[wv][3 * e] = chi; s_feat[wv][3 * e + 1] = clo; s_feat[wv][3 * e + 2] = chi;
+            }
+        }
+    }
     // ---- which joints MOVE in this call: varflag[j] = epoch as soon as one frame's inputs of joint j differ (bitwise) from frame 0's.
     // A joint nobody marks has the same rotation -- the same nine pose features -- in every frame: its correctives are a constant of the
     // call (k_lbs_still; a body-only solve leaves the 30 hand joints of SMPL-H at the hand prior's mean: chmosh.py:626-647 with
@@ -369,7 +491,7 @@ __global__ __launch_bounds__(64 * LBS_PREP_WAVES, LBS_PREP_WAVES == 16 ? 1 : 4) 
             const float id = (e == 0 || e == 4 || e == 8) ? 1.0f : 0.0f;
             const float d = a * Km[e] + b * K2[e];
             Rl[e] = id + d;
-            if (act && j >= 1) s_feat[wv][(j - 1) * 9 + e] = (_Float16)d;
+            if (act && j >= 1) s_feat[wv][fpose + (j - 1) * 9 + e] = (_Float16)d;
         }
     }
     PREP_STAMP(2)
@@ -424,12 +546,16 @@ __global__ __launch_bounds__(64 * LBS_PREP_WAVES, LBS_PREP_WAVES == 16 ? 1 : 4) 
     // requests per call, the waves a third of their time at the issue stage behind them).
     __syncthreads();
     {
-        const int fi = threadIdx.x & (LBS_PREP_WAVES - 1), g = threadIdx.x / LBS_PREP_WAVES, fo = fbase + fi;
-        if (g < KS * 4 && fo < F) {
-            const f32x4 piece = *reinterpret_cast<const f32x4*>(&s_feat[fi][g * 8]);
-            _Float16* dst = featF + ((((size_t)(fo >> 7) * KS + (g >> 2)) * 8 + ((fo >> 4) & 7)) * 64 + (fo & 15) + 16 * (g & 3)) * 8;
-            *reinterpret_cast<f32x4*>(dst) = piece;
-        }
+        const int fi = threadIdx.x & (LBS_PREP_WAVES - 1), fo = fbase + fi;
+        int g = threadIdx.x / LBS_PREP_WAVES;
+        do {   // (one piece a thread without a block: KS <= 16; with one, up to 28 k-steps = 112 pieces a frame)
+            if (g < KS * 4 && fo < F) {
+                const f32x4 piece = *reinterpret_cast<const f32x4*>(&s_feat[fi][g * 8]);
+                _Float16* dst = featF + ((((size_t)(fo >> 7) * KS + (g >> 2)) * 8 + ((fo >> 4) & 7)) * 64 + (fo & 15) + 16 * (g & 3)) * 8;
+                *reinterpret_cast<f32x4*>(dst) = piece;
+            }
+            g += 64;
+        } while (SH && g < KS * 4);
     }
     PREP_STAMP(5)
 #undef PREP_STAMP
@@ -498,17 +624,19 @@ __global__ __launch_bounds__(64 * LBS_PREP_WAVES, LBS_PREP_WAVES == 16 ? 1 : 4) 
 // export kernel would read, against frame 0's features -- and writes  pscale x (rest + still correctives)  in the layout of the rest
 // positions (tab_vsc): the start value of the export kernel's accumulators, whose k-loop then ends at kseff.  A body-only Stage-II
 // result (the reference's default: optimize_fingers off) keeps the 30 hand joints of SMPL-H still: 9 of 15 k-steps.
+// (SH: the extended layout -- KSX shape k-steps, which change per frame and so always stay in the export's loop, in front of the pose k-steps)
+template <bool SH>
 __global__ __launch_bounds__(64, 1) void k_lbs_still(Lbs32Model lm, const int* __restrict__ varflag, int epoch, int all_move) {
-    const int lane = threadIdx.x, g = blockIdx.x, KS = lm.KS, q4 = lane >> 4, fl = lane & 15;
+    const int lane = threadIdx.x, g = blockIdx.x, ksx = SH ? lm.KSX : 0, KS = lm.KS + ksx, q4 = lane >> 4, fl = lane & 15;
     int kseff = KS;
     if (!all_move) {
         const bool moves = lane >= 1 && lane < lm.K && varflag[min(lane, lm.K - 1)] == epoch;
         const unsigned long long mv = __ballot(moves);
         const int jl = mv ? 63 - __builtin_clzll(mv) : 0;
-        kseff = min(KS, (9 * jl + 31) / 32);
+        kseff = min(KS, ksx + (9 * jl + 31) / 32);
     }
     const __amdgpu_buffer_rsrc_t rs_feat = __builtin_amdgcn_make_buffer_rsrc((void*)lm.featF, 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_pf = __builtin_amdgcn_make_buffer_rsrc((void*)lm.Pfrag, 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_pf = __builtin_amdgcn_make_buffer_rsrc((void*)(SH ? lm.PfragX : lm.Pfrag), 0, 0x7fffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_tab = __builtin_amdgcn_make_buffer_rsrc((void*)lm.tables, 0, 0x7fffffff, 0x00020000);
     f32x4 vs[4], acc[3];
 #pragma unroll
@@ -540,11 +668,16 @@ __global__ __launch_bounds__(64, 1) void k_lbs_still(Lbs32Model lm, const int* _
     }
 }
 
+// SH (an instantiation of its own; the one without is the code as it was): the call carries coefficients of the free shape block.  The
+// k-loop is the same loop over a longer row: KSX shape k-steps in front (PfragX / k_lbs_prep<true>'s features), always run, then the
+// moving joints' pose k-steps.
+template <bool SH>
 __global__ __launch_bounds__(256, 2) void k_lbs_export(Lbs32Model lm, int V, int F, int NVT, int NFT, float* __restrict__ out, const int* __restrict__ varflag, int epoch,
                                                      long long* __restrict__ dbgbuf, int dbg) {
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int KS = lm.KS, NRM = lm.NRM;
+    const int ksx = SH ? lm.KSX : 0;
+    const int KS = SH ? lm.KS + ksx : lm.KS, NRM = lm.NRM;
     // k-steps [kseff, KS) hold features of joints that do not move in this call (k_lbs_prep's varflag): the same in every frame -- their
     // correctives are a per-vertex constant of the call, which k_lbs_still has added to the rest positions the accumulators start at
     // (tab_vsc); the k-loop runs the first kseff steps.  (dbg & 8: treat every joint as moving.)
@@ -553,7 +686,7 @@ __global__ __launch_bounds__(256, 2) void k_lbs_export(Lbs32Model lm, int V, int
         const bool moves = lane >= 1 && lane < lm.K && varflag[min(lane, lm.K - 1)] == epoch;
         const unsigned long long mv = __ballot(moves);
         const int jl = mv ? 63 - __builtin_clzll(mv) : 0;          // the last moving joint: its features end at 9 jl
-        kseff = __builtin_amdgcn_readfirstlane(min(KS, (9 * jl + 31) / 32));
+        kseff = __builtin_amdgcn_readfirstlane(min(KS, SH ? ksx + (9 * jl + 31) / 32 : (9 * jl + 31) / 32));
     }
     const unsigned tlb = (unsigned)lm.KJ * LX_JBYTES;      // bytes of one 16-frame block's transforms
     char* ring = lds_raw;                                  // [LX_RING][8 frame blocks][64 lanes][16 B]
@@ -592,7 +725,7 @@ __global__ __launch_bounds__(256, 2) void k_lbs_export(Lbs32Model lm, int V, int
     // Resource words: base, no stride, 2^31 - 1 bytes, raw 32-bit data format.
     const __amdgpu_buffer_rsrc_t rs_atr = __builtin_amdgcn_make_buffer_rsrc((void*)lm.Atr, 0, 0x7fffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_feat = __builtin_amdgcn_make_buffer_rsrc((void*)lm.featF, 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_pf = __builtin_amdgcn_make_buffer_rsrc((void*)lm.Pfrag, 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_pf = __builtin_amdgcn_make_buffer_rsrc((void*)(SH ? lm.PfragX : lm.Pfrag), 0, 0x7fffffff, 0x00020000);
     // (the small per-tile tables as well -- ONE kind of vector load in the kernel -- and all of them behind one resource: the model keeps
     //  them in one allocation, lm.tab_* are the tables' byte offsets in it; a resource is four scalar registers)
     const __amdgpu_buffer_rsrc_t rs_tab = __builtin_amdgcn_make_buffer_rsrc((void*)lm.tables, 0, 0x7fffffff, 0x00020000);
@@ -867,6 +1000,7 @@ extern "C" void moshii_lbs32_free(void* l32) {
     free_ptr(lm->v_shaped); free_ptr(lm->posedirs_t); free_ptr(lm->weights); free_ptr(lm->J);
     free_ptr(lm->Pfrag); free_ptr(lm->perm); free_ptr(lm->tables); free_ptr(lm->dbgbuf);
     free_ptr(lm->Atr); free_ptr(lm->featF); free_ptr(lm->hcompf); free_ptr(lm->hmeanf); free_ptr(lm->varflag); free_ptr(lm->jtab); free_ptr(lm->hcj);
+    free_ptr(lm->PfragX); free_ptr(lm->JSf); free_ptr(lm->Sft);
     memset(lm, 0, sizeof(*lm));
 }
 
@@ -1032,6 +1166,44 @@ extern "C" int moshii_lbs32_prepare(moshii_model_t m) {
             lm->mfma_ok = 1;
         }
     }
+    // ---- the free shape block (declared, changed or cleared since the last prepare: moshii_model_set_free_shape clears l32_valid)
+    {
+        if (hipDeviceSynchronize() != hipSuccess) return MOSHII_ERR_HIP;
+        free_ptr(lm->PfragX); free_ptr(lm->JSf); free_ptr(lm->Sft);
+        lm->PfragX = nullptr; lm->JSf = nullptr; lm->Sft = nullptr; lm->nshape = 0; lm->KSX = 0; lm->sxscale = 1.0f;
+        int NB = 0, start = 0, E = 0;
+        const double* JS = nullptr;
+        const double* sd = moshii_internal_shape_block(m, &NB, &start, &E, &JS);
+        if (E > 0) {
+            if (hipMalloc((void**)&lm->JSf, (size_t)K * E * 4 * sizeof(float)) != hipSuccess) return MOSHII_ERR_HIP;
+            if (hipMalloc((void**)&lm->Sft, (size_t)E * 3 * Vp * sizeof(float)) != hipSuccess) return MOSHII_ERR_HIP;
+            hipLaunchKernelGGL(k_cvt_js, dim3((K * E + 255) / 256), dim3(256), 0, 0, K * E, JS, lm->JSf);
+            hipLaunchKernelGGL(k_cvt_shapedirs, dim3(1024), dim3(256), 0, 0, V, Vp, NB, start, E, sd, lm->Sft);
+            lm->nshape = E;
+            // (k_lbs_prep<true> keeps a frame's feature row in LDS: bodies whose pose and shape k-steps pass its size take the plain kernel)
+            if (lm->mfma_ok && lm->KS + (3 * E + 31) / 32 <= LBS_PREP_KSMAX) {
+                double* d_part = nullptr;
+                if (hipMalloc((void**)&d_part, 256 * sizeof(double)) != hipSuccess) return MOSHII_ERR_HIP;
+                hipLaunchKernelGGL(k_absmax_block, dim3(256), dim3(256), 0, 0, (size_t)V * 3, NB, start, E, sd, d_part);
+                double part[256];
+                if (hipMemcpy(part, d_part, sizeof(part), hipMemcpyDeviceToHost) != hipSuccess) return MOSHII_ERR_HIP;
+                hipFree(d_part);
+                double dmax = 0.0;
+                for (double p : part) dmax = std::max(dmax, p);
+                // Operand scales.  The accumulators carry pscale x metres; the block's directions can be far larger than the pose
+                // correctives pscale was chosen for, so they are DIVIDED by a power of two sxscale that puts the largest at 2^7 .. 2^8
+                // and the coefficients multiplied by it: both halves of both operands' (hi, lo) pairs then stay f16 normals with bits
+                // to spare for centimetre-scale directions and coefficients of order 1, and nothing overflows below |c| ~ 100.
+                double sx = 1.0;
+                if (dmax > 0.0) sx = std::ldexp(1.0, (int)std::ceil(std::log2(dmax * (double)lm->pscale)) - 8);
+                lm->sxscale = (float)sx;
+                lm->KSX = (3 * E + 31) / 32;
+                const int NG = lm->NVT * 4, KST = lm->KSX + lm->KS;
+                if (hipMalloc((void**)&lm->PfragX, (size_t)NG * 3 * KST * 64 * 8 * sizeof(_Float16)) != hipSuccess) return MOSHII_ERR_HIP;
+                hipLaunchKernelGGL(k_pack_pfrag_shape, dim3(4096), dim3(256), 0, 0, NB, start, E, lm->KSX, lm->KS, NG, (double)lm->pscale / sx, lm->perm, sd, lm->Pfrag, lm->PfragX);
+            }
+        }
+    }
     hipLaunchKernelGGL(k_cvt_vsh, dim3((V * 3 + 255) / 256), dim3(256), 0, 0, V * 3, moshii_internal_vsh(m), lm->v_shaped);
     hipLaunchKernelGGL(k_cvt_vsh, dim3(1), dim3(256), 0, 0, K * 3, moshii_internal_J(m), lm->J);
     lm->jtab_valid = 0;
@@ -1050,26 +1222,29 @@ extern "C" int moshii_internal_lbs_debug_times(void* lbs32, long long* out512x2)
 }
 
 extern "C" hipError_t moshii_launch_lbs_f32(hipStream_t stream, const ModelDev* md, int F, const float* pose,
-                                            const float* trans, float* verts, void* lbs32) {
+                                            const float* trans, const float* shape, float* verts, void* lbs32) {
     Lbs32Model* lmp = (Lbs32Model*)lbs32;
     const bool force_v0 = getenv("MOSHII_LBS_PLAIN") != nullptr;   // the plain f32 kernel (tests compare the two)
-    if (!lmp->mfma_ok || force_v0) {
+    const bool sh = shape != nullptr && lmp->nshape > 0;           // per-frame coefficients of the free shape block
+    if (!lmp->mfma_ok || force_v0 || (sh && !lmp->PfragX)) {
         const Lbs32Model lm = *lmp;
-        const size_t lds = (size_t)(md->P + md->K * 30) * sizeof(float);
-        hipLaunchKernelGGL(k_lbs_f32_v0, dim3((md->V + 255) / 256, F), dim3(256), lds, stream, *md, lm, pose, trans, verts);
+        const size_t lds = (size_t)(md->P + md->K * 33) * sizeof(float);
+        hipLaunchKernelGGL(k_lbs_f32_v0, dim3((md->V + 255) / 256, F), dim3(256), lds, stream, *md, lm, pose, trans, sh ? shape : (const float*)nullptr, verts);
         return hipGetLastError();
     }
+    const int KSU = sh ? lmp->KS + lmp->KSX : lmp->KS;             // k-steps of this call's feature rows
     // The export kernel addresses the per-call scratch through buffer resources (2^31 - 1 bytes, 32-bit offsets; a load beyond the range
     // returns zeros, silently): a call that would pass that is cut into sub-calls of whole frame tiles (SMPL-H: 860 000 frames a piece).
     {
-        const long long per16 = (long long)lmp->KJ * LX_JBYTES, per128 = (long long)lmp->KS * LX_CHUNK;
+        const long long per16 = (long long)lmp->KJ * LX_JBYTES, per128 = (long long)KSU * LX_CHUNK;
         long long fmax = std::min(((0x7fffffffLL - 4096) / per16) * 16, ((0x7fffffffLL - 4096) / per128) * LX_TF);
         if (const char* es = getenv("MOSHII_LBS_FMAX")) fmax = std::min(fmax, (long long)std::max(LX_TF, atoi(es)));   // (tests: a small limit)
         fmax = fmax / LX_TF * LX_TF;
         if ((long long)F > fmax) {
             for (long long f0 = 0; f0 < F; f0 += fmax) {
                 const int n = (int)std::min<long long>(fmax, F - f0);
-                hipError_t e = moshii_launch_lbs_f32(stream, md, n, pose + (size_t)f0 * md->NP, trans + (size_t)f0 * 3, verts + (size_t)f0 * md->V * 3, lbs32);
+                hipError_t e = moshii_launch_lbs_f32(stream, md, n, pose + (size_t)f0 * md->NP, trans + (size_t)f0 * 3,
+                                                     sh ? shape + (size_t)f0 * lmp->nshape : (const float*)nullptr, verts + (size_t)f0 * md->V * 3, lbs32);
                 if (e != hipSuccess) return e;
             }
             return hipSuccess;
@@ -1078,19 +1253,29 @@ extern "C" hipError_t moshii_launch_lbs_f32(hipStream_t stream, const ModelDev* 
     const int Fpad = (F + LX_TF - 1) / LX_TF * LX_TF;
     if (Fpad > lmp->Fcap) {   // per-call scratch grows to the largest F seen (not stream-ordered: sync first)
         hipStreamSynchronize(stream);
-        free_ptr(lmp->Atr); free_ptr(lmp->featF);
-        lmp->Atr = nullptr; lmp->featF = nullptr; lmp->Fcap = 0;
-        const size_t na = (size_t)(Fpad / 16) * lmp->KJ * LX_JBYTES, nf = (size_t)(Fpad / LX_TF) * lmp->KS * LX_CHUNK;
+        free_ptr(lmp->Atr);
+        lmp->Atr = nullptr; lmp->Fcap = 0;
+        const size_t na = (size_t)(Fpad / 16) * lmp->KJ * LX_JBYTES;
         hipError_t e = hipMalloc((void**)&lmp->Atr, na);
         if (e != hipSuccess) return e;
-        e = hipMalloc((void**)&lmp->featF, nf);
-        if (e != hipSuccess) return e;
-        // frames beyond F, joints beyond K and feature columns beyond 9 (K - 1) are never written again: they stay zero
+        // frames beyond F and joints beyond K are never written again: they stay zero
         e = hipMemset(lmp->Atr, 0, na);
         if (e != hipSuccess) return e;
-        e = hipMemset(lmp->featF, 0, nf);
-        if (e != hipSuccess) return e;
         lmp->Fcap = Fpad;
+    }
+    {   // the features likewise, by bytes: a row has KS k-steps, or KSX + KS in a call with shape coefficients
+        const long long nf = (long long)(Fpad / LX_TF) * KSU * LX_CHUNK;
+        if (nf > lmp->featcap) {
+            hipStreamSynchronize(stream);
+            free_ptr(lmp->featF);
+            lmp->featF = nullptr; lmp->featcap = 0;
+            hipError_t e = hipMalloc((void**)&lmp->featF, (size_t)nf);
+            if (e != hipSuccess) return e;
+            // (every call writes the whole rows of its frames; frames beyond F are computed and dropped: finite values, zero at first)
+            e = hipMemset(lmp->featF, 0, (size_t)nf);
+            if (e != hipSuccess) return e;
+            lmp->featcap = nf;
+        }
     }
     if (!lmp->hmeanf) {   // f32 copies of the hand-pose map (stream-ordered: ahead of the first k_lbs_prep that reads them)
         const int nh = std::max(md->nhand_full, 1), nc = std::max(md->hand_dof * md->nhand_full, 1);
@@ -1125,9 +1310,17 @@ extern "C" hipError_t moshii_launch_lbs_f32(hipStream_t stream, const ModelDev* 
     const Lbs32Model lm = *lmp;
     int dbg = 0;
     if (const char* es = getenv("MOSHII_LBS_STOP")) dbg = atoi(es) & 127;   // (development: phase timing by truncation / clock stamps; incomplete output)
-    hipLaunchKernelGGL(k_lbs_prep, dim3(LBS_PREP_WAVES == 16 ? (F + 15) / 16 : ((F + 127) / 128) * 32), dim3(64 * LBS_PREP_WAVES), 0, stream, *md, lm.jtab, lm.hcj, lm.hcompf, F, lm.KS, lm.KJ, pose, trans, lm.Atr, lm.featF, lm.varflag, lm.epoch,
-                       (dbg & 16) ? lm.dbgbuf + 8 * 24 : (long long*)nullptr);
-    hipLaunchKernelGGL(k_lbs_still, dim3(lm.NVT * 4), dim3(64), 0, stream, lm, lm.varflag, lm.epoch, (dbg & 8) ? 1 : 0);
+    const dim3 pgrid(LBS_PREP_WAVES == 16 ? (F + 15) / 16 : ((F + 127) / 128) * 32);
+    long long* const pstamps = (dbg & 16) ? lm.dbgbuf + 8 * 24 : (long long*)nullptr;
+    if (sh) {
+        hipLaunchKernelGGL(k_lbs_prep<true>, pgrid, dim3(64 * LBS_PREP_WAVES), 0, stream, *md, lm.jtab, lm.hcj, lm.hcompf, F, KSU, lm.KJ, pose, trans, lm.Atr, lm.featF, lm.varflag, lm.epoch,
+                           pstamps, lm.JSf, shape, lm.nshape, lm.KSX, lm.sxscale);
+        hipLaunchKernelGGL(k_lbs_still<true>, dim3(lm.NVT * 4), dim3(64), 0, stream, lm, lm.varflag, lm.epoch, (dbg & 8) ? 1 : 0);
+    } else {
+        hipLaunchKernelGGL(k_lbs_prep<false>, pgrid, dim3(64 * LBS_PREP_WAVES), 0, stream, *md, lm.jtab, lm.hcj, lm.hcompf, F, lm.KS, lm.KJ, pose, trans, lm.Atr, lm.featF, lm.varflag, lm.epoch,
+                           pstamps, (const float*)nullptr, (const float*)nullptr, 0, 0, 1.0f);
+        hipLaunchKernelGGL(k_lbs_still<false>, dim3(lm.NVT * 4), dim3(64), 0, stream, lm, lm.varflag, lm.epoch, (dbg & 8) ? 1 : 0);
+    }
     const int NVT = lm.NVT, NFT = Fpad / LX_TF;
     int ncu = 0, devid = 0;
     hipGetDevice(&devid);
@@ -1135,8 +1328,10 @@ extern "C" hipError_t moshii_launch_lbs_f32(hipStream_t stream, const ModelDev* 
     // two workgroups per CU (a workgroup takes half a CU's registers and LDS), 8 XCDs
     int nslots = std::max(1, std::min(2 * (ncu > 0 ? ncu : 256) / 8, ((NVT + 7) / 8) * NFT));
     if (const char* es = getenv("MOSHII_LBS_SLOTS")) nslots = std::max(1, std::min(nslots, atoi(es)));   // (development: fewer workgroups per XCD)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_lbs_export), hipFuncAttributeMaxDynamicSharedMemorySize, LX_LDS_BYTES);
+    hipError_t e = hipFuncSetAttribute(sh ? reinterpret_cast<const void*>(k_lbs_export<true>) : reinterpret_cast<const void*>(k_lbs_export<false>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, LX_LDS_BYTES);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_lbs_export, dim3(8 * nslots), dim3(256), LX_LDS_BYTES, stream, lm, md->V, F, NVT, NFT, verts, lm.varflag, lm.epoch, lm.dbgbuf, dbg);
+    if (sh) hipLaunchKernelGGL(k_lbs_export<true>, dim3(8 * nslots), dim3(256), LX_LDS_BYTES, stream, lm, md->V, F, NVT, NFT, verts, lm.varflag, lm.epoch, lm.dbgbuf, dbg);
+    else hipLaunchKernelGGL(k_lbs_export<false>, dim3(8 * nslots), dim3(256), LX_LDS_BYTES, stream, lm, md->V, F, NVT, NFT, verts, lm.varflag, lm.epoch, lm.dbgbuf, dbg);
     return hipGetLastError();
 }

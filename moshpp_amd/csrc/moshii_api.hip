@@ -19,7 +19,7 @@ extern "C" hipError_t moshii_launch_markers(int F, size_t lds_bytes, hipStream_t
                                             const ModelDev* md, const ChainLayout* ly, const double* pose,
                                             const double* trans, double* out);
 extern "C" hipError_t moshii_launch_lbs_f32(hipStream_t stream, const ModelDev* md, int F, const float* pose,
-                                            const float* trans, float* verts, void* lbs32);
+                                            const float* trans, const float* shape, float* verts, void* lbs32);
 
 namespace {
 
@@ -196,9 +196,13 @@ __global__ void k_pack_shape(int Nv, int Nvp, int NB, int start, int E, const in
 }
 
 // Reference-precision full-mesh LBS: one block = 256 vertices of one frame.
+// SH: a row of free-shape coefficients per frame (moshii_lbs_forward_shape_f64): the rest positions gain the block's columns of
+// shapedirs, the joints JS . shape[f] (LDS copy sJ); without it the frozen rest positions and joints, as before.
+template <bool SH>
 __global__ void k_lbs_f64(ModelDev md, const double* __restrict__ vsh, const double* __restrict__ posedirs,
                           const double* __restrict__ weights, const double* __restrict__ pose,
-                          const double* __restrict__ trans, double* __restrict__ out) {
+                          const double* __restrict__ trans, double* __restrict__ out,
+                          const double* __restrict__ shapedirs, int NB, int sstart, const double* __restrict__ shape) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int K = md.K, P = md.P;
     double* fullpose = sm;            // P
@@ -206,7 +210,18 @@ __global__ void k_lbs_f64(ModelDev md, const double* __restrict__ vsh, const dou
     double* Rw = Rl + K * 9;          // K*9
     double* tw = Rw + K * 9;          // K*3
     double* feat = tw + K * 3;        // K*9
+    double* sJ = feat + K * 9;        // K*3 (SH only): this frame's joints
     const int f = blockIdx.y, tid = threadIdx.x;
+    const int E = SH ? md.nshape : 0;
+    const double* cf = SH ? shape + (size_t)f * E : nullptr;
+    if (SH) {
+        for (int d = tid; d < K * 3; d += blockDim.x) {
+            double s = md.J[d];
+            for (int e = 0; e < E; ++e) s += md.JS[((size_t)(d / 3) * E + e) * 3 + d % 3] * cf[e];
+            sJ[d] = s;
+        }
+    }
+    auto Jat = [&](int d) -> double { if (SH) return sJ[d]; return md.J[d]; };
     const double* ps = pose + (size_t)f * md.NP;
     for (int d = tid; d < P; d += blockDim.x) {
         double v;
@@ -237,15 +252,15 @@ __global__ void k_lbs_f64(ModelDev md, const double* __restrict__ vsh, const dou
     __syncthreads();
     if (tid == 0) {   // serial chain: K <= 64 joints
         for (int e = 0; e < 9; ++e) Rw[e] = Rl[e];
-        for (int i = 0; i < 3; ++i) tw[i] = md.J[i];
+        for (int i = 0; i < 3; ++i) tw[i] = Jat(i);
         for (int k = 1; k < K; ++k) {
             const int p = md.parents[k];
             for (int i = 0; i < 3; ++i) {
                 for (int j = 0; j < 3; ++j)
                     Rw[k * 9 + i * 3 + j] = Rw[p * 9 + i * 3 + 0] * Rl[k * 9 + 0 * 3 + j] + Rw[p * 9 + i * 3 + 1] * Rl[k * 9 + 1 * 3 + j] +
                                             Rw[p * 9 + i * 3 + 2] * Rl[k * 9 + 2 * 3 + j];
-                tw[k * 3 + i] = Rw[p * 9 + i * 3 + 0] * (md.J[k * 3 + 0] - md.J[p * 3 + 0]) + Rw[p * 9 + i * 3 + 1] * (md.J[k * 3 + 1] - md.J[p * 3 + 1]) +
-                                Rw[p * 9 + i * 3 + 2] * (md.J[k * 3 + 2] - md.J[p * 3 + 2]) + tw[p * 3 + i];
+                tw[k * 3 + i] = Rw[p * 9 + i * 3 + 0] * (Jat(k * 3 + 0) - Jat(p * 3 + 0)) + Rw[p * 9 + i * 3 + 1] * (Jat(k * 3 + 1) - Jat(p * 3 + 1)) +
+                                Rw[p * 9 + i * 3 + 2] * (Jat(k * 3 + 2) - Jat(p * 3 + 2)) + tw[p * 3 + i];
             }
         }
     }
@@ -258,13 +273,17 @@ __global__ void k_lbs_f64(ModelDev md, const double* __restrict__ vsh, const dou
         const double* row = posedirs + ((size_t)v * 3 + i) * nfeat;
         double s = 0.0;
         for (int q = 0; q < nfeat; ++q) s += row[q] * feat[9 + q];
+        if (SH) {
+            const double* srow = shapedirs + ((size_t)v * 3 + i) * NB + sstart;
+            for (int e = 0; e < E; ++e) s += srow[e] * cf[e];
+        }
         vp[i] = vsh[v * 3 + i] + s;
     }
     double acc[3] = {0.0, 0.0, 0.0};
     for (int j = 0; j < K; ++j) {
         const double w = weights[(size_t)v * K + j];
         if (w == 0.0) continue;
-        const double dx = vp[0] - md.J[j * 3 + 0], dy = vp[1] - md.J[j * 3 + 1], dz = vp[2] - md.J[j * 3 + 2];
+        const double dx = vp[0] - Jat(j * 3 + 0), dy = vp[1] - Jat(j * 3 + 1), dz = vp[2] - Jat(j * 3 + 2);
         for (int i = 0; i < 3; ++i)
             acc[i] += w * (Rw[j * 9 + i * 3 + 0] * dx + Rw[j * 9 + i * 3 + 1] * dy + Rw[j * 9 + i * 3 + 2] * dz + tw[j * 3 + i]);
     }
@@ -335,7 +354,7 @@ struct LaunchInfo { std::string name; int lds = 0; int threads = 0; } g_last;
 extern "C" {
 
 const char* moshii_last_error(void) { return g_err.c_str(); }
-int moshii_version(void) { return 102; }   // 101: moshii_stagei_desc grew by init_sq; 102: moshii_solve_opts by the joint-angle term (include/moshii.h)
+int moshii_version(void) { return 103; }   // 101: moshii_stagei_desc grew by init_sq; 102: moshii_solve_opts by the joint-angle term; 103: moshii_lbs_forward_shape_* (include/moshii.h)
 #ifndef MOSHII_SRC_HASH
 #define MOSHII_SRC_HASH "unknown"
 #endif
@@ -469,6 +488,7 @@ int moshii_model_set_free_shape(moshii_model_t m, int32_t start, int32_t count) 
     HIP_TRY(hipDeviceSynchronize());
     if (m->d_JS) { hipFree(m->d_JS); m->d_JS = nullptr; }
     m->shape_start = start; m->nshape = count;
+    m->l32_valid = false;   // the f32 export's fragments and scratch sizes depend on the block
     if (count == 0) return MOSHII_OK;
     HIP_TRY(hipMalloc((void**)&m->d_JS, (size_t)m->K * count * 3 * sizeof(double)));
     hipLaunchKernelGGL(k_shape_joints, dim3(m->K * count), dim3(256), 0, 0, m->V, m->NB, start, count, m->d_Jreg, m->d_shapedirs, m->d_JS);
@@ -483,62 +503,97 @@ int moshii_model_get_joints(moshii_model_t m, double* J_out) {
     return MOSHII_OK;
 }
 
-int moshii_lbs_forward_f64(moshii_model_t m, int32_t F, const double* pose, const double* trans, double* verts,
-                           uint32_t flags, void* stream_) {
+// shape: per-frame coefficients of the free block [F][nshape], or null (the frozen body)
+static int lbs_forward_f64_impl(moshii_model_t m, int32_t F, const double* pose, const double* trans, const double* shape, double* verts,
+                                uint32_t flags, void* stream_) {
     if (!m || !pose || !trans || !verts || F < 0) return fail(MOSHII_ERR_ARG, "bad argument");
+    if (shape && m->nshape == 0) return fail(MOSHII_ERR_ARG, "shape coefficients without a block: call moshii_model_set_free_shape first");
     if (F == 0) return MOSHII_OK;
     hipStream_t stream = (hipStream_t)stream_;
     const bool dev = (flags & MOSHII_BUFFERS_DEVICE) != 0;
-    const double *d_pose = pose, *d_trans = trans;
+    const double *d_pose = pose, *d_trans = trans, *d_shape = shape;
     double* d_out = verts;
-    double *t_pose = nullptr, *t_trans = nullptr, *t_out = nullptr;
+    double *t_pose = nullptr, *t_trans = nullptr, *t_shape = nullptr, *t_out = nullptr;
     if (!dev) {
         int rc;
         if ((rc = dev_upload(pose, (size_t)F * m->NP, &t_pose))) return rc;
         if ((rc = dev_upload(trans, (size_t)F * 3, &t_trans))) return rc;
+        if (shape && (rc = dev_upload(shape, (size_t)F * m->nshape, &t_shape))) return rc;
         HIP_TRY(hipMalloc((void**)&t_out, (size_t)F * m->V * 3 * sizeof(double)));
         d_pose = t_pose; d_trans = t_trans; d_out = t_out;
+        if (shape) d_shape = t_shape;
     }
-    const size_t lds = (size_t)(m->P + m->K * 30) * sizeof(double);
-    hipLaunchKernelGGL(k_lbs_f64, dim3((m->V + 255) / 256, F), dim3(256), lds, stream, m->dev(), m->d_vsh, m->d_posedirs,
-                       m->d_weights, d_pose, d_trans, d_out);
+    if (d_shape) {
+        const size_t lds = (size_t)(m->P + m->K * 33) * sizeof(double);
+        hipLaunchKernelGGL(k_lbs_f64<true>, dim3((m->V + 255) / 256, F), dim3(256), lds, stream, m->dev(), m->d_vsh, m->d_posedirs,
+                           m->d_weights, d_pose, d_trans, d_out, m->d_shapedirs, m->NB, m->shape_start, d_shape);
+    } else {
+        const size_t lds = (size_t)(m->P + m->K * 30) * sizeof(double);
+        hipLaunchKernelGGL(k_lbs_f64<false>, dim3((m->V + 255) / 256, F), dim3(256), lds, stream, m->dev(), m->d_vsh, m->d_posedirs,
+                           m->d_weights, d_pose, d_trans, d_out, (const double*)nullptr, 0, 0, (const double*)nullptr);
+    }
     HIP_TRY(hipGetLastError());
     if (!dev) {
         HIP_TRY(hipStreamSynchronize(stream));
         HIP_TRY(hipMemcpy(verts, t_out, (size_t)F * m->V * 3 * sizeof(double), hipMemcpyDeviceToHost));
         hipFree(t_pose); hipFree(t_trans); hipFree(t_out);
+        if (t_shape) hipFree(t_shape);
     }
     return MOSHII_OK;
+}
+
+int moshii_lbs_forward_f64(moshii_model_t m, int32_t F, const double* pose, const double* trans, double* verts,
+                           uint32_t flags, void* stream) {
+    return lbs_forward_f64_impl(m, F, pose, trans, nullptr, verts, flags, stream);
+}
+
+int moshii_lbs_forward_shape_f64(moshii_model_t m, int32_t F, const double* pose, const double* trans, const double* shape,
+                                 double* verts, uint32_t flags, void* stream) {
+    return lbs_forward_f64_impl(m, F, pose, trans, shape, verts, flags, stream);
 }
 
 // implemented in lbs_forward.hip
 int moshii_lbs32_prepare(moshii_model_t m);
 
-int moshii_lbs_forward_f32(moshii_model_t m, int32_t F, const float* pose, const float* trans, float* verts,
-                           uint32_t flags, void* stream_) {
+static int lbs_forward_f32_impl(moshii_model_t m, int32_t F, const float* pose, const float* trans, const float* shape, float* verts,
+                                uint32_t flags, void* stream_) {
     if (!m || !pose || !trans || !verts || F < 0) return fail(MOSHII_ERR_ARG, "bad argument");
+    if (shape && m->nshape == 0) return fail(MOSHII_ERR_ARG, "shape coefficients without a block: call moshii_model_set_free_shape first");
     if (F == 0) return MOSHII_OK;
     hipStream_t stream = (hipStream_t)stream_;
     if (!m->l32_valid) { int rc = moshii_lbs32_prepare(m); if (rc) return rc; }
     const bool dev = (flags & MOSHII_BUFFERS_DEVICE) != 0;
-    const float *d_pose = pose, *d_trans = trans;
+    const float *d_pose = pose, *d_trans = trans, *d_shape = shape;
     float* d_out = verts;
-    float *t_pose = nullptr, *t_trans = nullptr, *t_out = nullptr;
+    float *t_pose = nullptr, *t_trans = nullptr, *t_shape = nullptr, *t_out = nullptr;
     if (!dev) {
         int rc;
         if ((rc = dev_upload(pose, (size_t)F * m->NP, &t_pose))) return rc;
         if ((rc = dev_upload(trans, (size_t)F * 3, &t_trans))) return rc;
+        if (shape && (rc = dev_upload(shape, (size_t)F * m->nshape, &t_shape))) return rc;
         HIP_TRY(hipMalloc((void**)&t_out, (size_t)F * m->V * 3 * sizeof(float)));
         d_pose = t_pose; d_trans = t_trans; d_out = t_out;
+        if (shape) d_shape = t_shape;
     }
     ModelDev md = m->dev();
-    HIP_TRY(moshii_launch_lbs_f32(stream, &md, F, d_pose, d_trans, d_out, &m->l32));
+    HIP_TRY(moshii_launch_lbs_f32(stream, &md, F, d_pose, d_trans, d_shape, d_out, &m->l32));
     if (!dev) {
         HIP_TRY(hipStreamSynchronize(stream));
         HIP_TRY(hipMemcpy(verts, t_out, (size_t)F * m->V * 3 * sizeof(float), hipMemcpyDeviceToHost));
         hipFree(t_pose); hipFree(t_trans); hipFree(t_out);
+        if (t_shape) hipFree(t_shape);
     }
     return MOSHII_OK;
+}
+
+int moshii_lbs_forward_f32(moshii_model_t m, int32_t F, const float* pose, const float* trans, float* verts,
+                           uint32_t flags, void* stream) {
+    return lbs_forward_f32_impl(m, F, pose, trans, nullptr, verts, flags, stream);
+}
+
+int moshii_lbs_forward_shape_f32(moshii_model_t m, int32_t F, const float* pose, const float* trans, const float* shape,
+                                 float* verts, uint32_t flags, void* stream) {
+    return lbs_forward_f32_impl(m, F, pose, trans, shape, verts, flags, stream);
 }
 
 int moshii_prior_create(int32_t G, int32_t npose, const double* means, const double* chols, const double* weights,
@@ -1578,6 +1633,11 @@ const double* moshii_internal_posedirs(moshii_model_t m) { return m->d_posedirs;
 const double* moshii_internal_weights(moshii_model_t m) { return m->d_weights; }
 const double* moshii_internal_J(moshii_model_t m) { return m->d_J; }
 const double* moshii_internal_weights_host(moshii_model_t m) { return m->weights_host.data(); }
+// the free shape block: the device copy of shapedirs [V][3][NB], the block's first column and size, JS [K][nshape][3]
+const double* moshii_internal_shape_block(moshii_model_t m, int* NB, int* start, int* count, const double** JS) {
+    *NB = m->NB; *start = m->shape_start; *count = m->nshape; *JS = m->d_JS;
+    return m->d_shapedirs;
+}
 void* moshii_internal_l32(moshii_model_t m) { return &m->l32; }
 void moshii_internal_l32_set_valid(moshii_model_t m, int v) { m->l32_valid = v != 0; }
 }

@@ -257,4 +257,12 @@ struct Lbs32Model {
     float* Atr;            // [Fcap/16][KJ][16][12]  joint transforms, row major (R_i0, R_i1, R_i2, t_i), i = 0 .. 2: each float one B operand of the blend
     _Float16* featF;       // [Fcap/128][KS][8][64 lanes][8]  pose features, B-operand fragments
     int Fcap;
+    // free shape block (moshii_lbs_forward_shape_f32; all null / 0 without a block): the block's columns as KSX k-steps IN FRONT of the
+    // pose k-steps -- coefficient e is the three columns 3e (direction hi x coefficient hi), 3e + 1 (hi x lo), 3e + 2 (lo x hi)
+    _Float16* PfragX;      // [NVT*4 groups][3][KSX + KS][64 lanes][8]  shape columns * pscale / sxscale, then the pose fragments of Pfrag
+    float* JSf;            // [K][nshape][4]  f32 copy of JS (dJ/d coefficient), padded to 16 bytes
+    float* Sft;            // [nshape][3][Vp64]  f32 copy of the block's directions, vertex fastest (plain kernel)
+    int nshape, KSX;       // coefficients; k-steps of 32 shape columns (3 nshape, zero padded)
+    float sxscale;         // power of two: the coefficients are multiplied by it, the directions divided
+    long long featcap;     // bytes of featF (the extended layout needs more per frame tile)
 };

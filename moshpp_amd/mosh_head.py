@@ -278,3 +278,105 @@ def load_as_amass_npz(stageii_pkl_data_or_fname, stageii_npz_fname=None, stagei_
             np.savez(_makepath(str(stagei_npz_fname)), **{k: v for k, v in out.items() if k in _STAGEI_NPZ_KEYS})
             logger.info(f'created amass_stagei_npz_fname: {stagei_npz_fname}')
     return out
+
+
+def _stageii_vertices_plan(pkl, frame_ids):
+    """Everything stageii_vertices decides from the Stage-II dict alone, checked before a model is loaded or a device touched:
+    (cfg.surface_model, kind 'expr' | 'dmpl' | None, block start, block size, frame ids)."""
+    for k in ('fullpose', 'trans', 'betas', 'stageii_debug_details'):
+        if k not in pkl:
+            raise KeyError(f"stageii_vertices: the Stage-II data has no '{k}'")
+    if 'cfg' not in pkl['stageii_debug_details']:
+        raise KeyError("stageii_vertices: the Stage-II data has no stored cfg (stageii_debug_details['cfg'])")
+    cfg = pkl['stageii_debug_details']['cfg']
+    sm, mp = cfg['surface_model'], cfg['moshpp']
+    fullpose, trans = np.asarray(pkl['fullpose']), np.asarray(pkl['trans'])
+    if fullpose.ndim != 2 or trans.shape != (fullpose.shape[0], 3):
+        raise ValueError(f'stageii_vertices: fullpose {fullpose.shape} / trans {trans.shape} are not [T, 3K] / [T, 3]')
+    T = fullpose.shape[0]
+    face, dyn = bool(mp.get('optimize_face', False)), bool(mp.get('optimize_dynamics', False))
+    if face and dyn:
+        raise ValueError('stageii_vertices: optimize_face and optimize_dynamics are mutually exclusive')
+    if (face or 'expression' in pkl) and sm['type'] != 'smplx':
+        raise ValueError(f"stageii_vertices: expression coefficients belong to smplx, the stored model type is {sm['type']}")
+    if (dyn or 'dmpls' in pkl) and sm['type'] not in ('smpl', 'smplh'):
+        raise ValueError(f"stageii_vertices: DMPL coefficients belong to smpl / smplh, the stored model type is {sm['type']}")
+    kind, start, count = None, 0, 0
+    if face:
+        kind, start, count = 'expr', int(sm.get('betas_expr_start_id', 300)), int(sm.get('num_expressions', 80))
+        key = 'expression'
+    elif dyn:
+        kind, start, count = 'dmpl', int(sm['num_betas']), int(sm.get('num_dmpls', 8))
+        key = 'dmpls'
+    if kind is not None:
+        if key not in pkl:
+            raise KeyError(f"stageii_vertices: the cfg says optimize_{'face' if face else 'dynamics'} but the data has no '{key}'")
+        c = np.asarray(pkl[key])
+        if c.ndim != 2 or c.shape[0] != T or c.shape[1] < count:
+            raise ValueError(f"stageii_vertices: '{key}' is {c.shape}, expected [{T}, >= {count}]")
+    if frame_ids is None:
+        ids = np.arange(T)
+    else:
+        ids = np.atleast_1d(np.asarray(frame_ids))
+        if ids.ndim != 1 or not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError('stageii_vertices: frame_ids must be a list of integers')
+        if len(ids) and (ids.min() < 0 or ids.max() >= T):
+            raise IndexError(f'stageii_vertices: frame_ids outside the {T} solved frames')
+    return sm, mp, kind, start, count, ids
+
+
+def stageii_vertices(stageii_data_or_fname, surface_model=None, frame_ids=None, dtype=np.float32):
+    """verts[T, V, 3]: the meshes a Stage-II result (pickle file name or dict) describes, frame by frame -- pose, translation,
+    Stage-I betas AND, where the solve freed them, the per-frame expression (optimize_face, SMPL-X) or DMPL coefficients
+    (optimize_dynamics, SMPL / SMPL-H): rest positions and joints move with them exactly as they did in the solve, so the mesh
+    carries the solve's simulated markers.  Every other result (body / finger solves, MANO, the animal models) is a plain export.
+
+    surface_model: a models.SurfaceModel; default: the model file named by the stored cfg.  With optimize_dynamics the DMPL
+    directions of cfg.surface_model.dmpl_fname replace shapedirs[:, :, num_betas : num_betas + num_dmpls] as in the solve; a cfg
+    without dmpl_fname means the given surface_model already holds them there.  frame_ids: rows of the result (default: all).
+    dtype float32: the batched export kernels (|error| <= 2e-5 m); float64: the reference-precision kernel."""
+    if isinstance(stageii_data_or_fname, dict):
+        pkl = stageii_data_or_fname
+    else:
+        with open(stageii_data_or_fname, 'rb') as fh:
+            pkl = pickle.load(fh)
+    sm, mp, kind, start, count, ids = _stageii_vertices_plan(pkl, frame_ids)
+    from .models import load_surface_model
+    if surface_model is None:
+        surface_model = load_surface_model(surface_model_fname=sm['fname'], surface_model_type=sm['type'],
+                                           pose_hand_prior_fname=mp.get('pose_hand_prior_fname'),
+                                           use_hands_mean=sm.get('use_hands_mean', False), dof_per_hand=sm.get('dof_per_hand', 12),
+                                           v_template_fname=pkl.get('v_template_fname'))
+    K = surface_model.K
+    fullpose = np.asarray(pkl['fullpose'], dtype=np.float64)
+    if fullpose.shape[1] != 3 * K:
+        raise ValueError(f'stageii_vertices: fullpose has {fullpose.shape[1]} columns, the model {3 * K}')
+    shapedirs = np.asarray(surface_model.shapedirs, dtype=np.float64)
+    if kind == 'dmpl':
+        if shapedirs.shape[2] < start + count:
+            shapedirs = np.concatenate([shapedirs, np.zeros(shapedirs.shape[:2] + (start + count - shapedirs.shape[2],))], axis=2)
+        if sm.get('dmpl_fname'):
+            from .chmosh import read_dmpl_pcs
+            shapedirs = shapedirs.copy()
+            shapedirs[:, :, start:start + count] = np.asarray(read_dmpl_pcs(sm['dmpl_fname']), dtype=np.float64)[:, :, :count]
+    if kind is not None and start + count > shapedirs.shape[2]:
+        raise ValueError(f'stageii_vertices: the free block [{start}, {start + count}) exceeds the {shapedirs.shape[2]} shape '
+                         f'coefficients of the model')
+    nb = int(sm['num_betas'])
+    betas = np.asarray(pkl['betas'], dtype=np.float64).ravel()
+    b = np.zeros(shapedirs.shape[2])
+    b[:nb] = betas[:nb]                                   # as mosh_stageii applies them
+    coef = None
+    if kind is not None:   # stored: the frozen betas of those columns + the solved offsets
+        coef = np.asarray(pkl['expression' if kind == 'expr' else 'dmpls'], dtype=np.float64)[ids, :count] - b[start:start + count]
+    from . import capi
+    # the pickle holds the FULL pose: every joint's rotation vector is a pose variable of this handle (no hand-PCA map)
+    dev = capi.Model(surface_model.v_template, shapedirs, surface_model.posedirs, surface_model.weights, surface_model.J_regressor,
+                     surface_model.parents, 3 * K, 0)
+    try:
+        dev.set_betas(b)
+        if kind is not None:
+            dev.set_free_shape(start, count)
+        return dev.lbs_forward(fullpose[ids], np.asarray(pkl['trans'], dtype=np.float64)[ids], dtype=dtype, shape=coef)
+    finally:
+        dev.close()

@@ -1,7 +1,20 @@
-"""Time the full-mesh LBS export kernels alone (for rocprofv3): python tools/lbs_bench.py [F] [reps] [model]"""
+"""Time the full-mesh LBS export kernels alone (for rocprofv3): python tools/lbs_bench.py [F] [reps] [model] [--shape E] [--repeats N]
+--shape E: the export with per-frame coefficients of a free shape block of E columns (moshii_lbs_forward_shape_f32) -- the body gets E
+extra shapedirs columns (a unit coefficient moves a vertex by up to 1 cm), the coefficients are N(0, 1); same poses otherwise.
+--repeats N: N timed rounds of `reps` calls each, one line per round (run-to-run spread)."""
 import ctypes as C, sys, time
 import numpy as np
 sys.path.insert(0, '.')
+E_SHAPE, REPEATS = 0, 1
+for flag in ('--shape', '--repeats'):
+    if flag in sys.argv:
+        i = sys.argv.index(flag)
+        val = int(sys.argv[i + 1])
+        del sys.argv[i:i + 2]
+        if flag == '--shape':
+            E_SHAPE = val
+        else:
+            REPEATS = val
 import torch
 from moshpp_amd import capi, workload
 F = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
@@ -14,8 +27,17 @@ from moshpp_amd import synth
 order = os.environ.get('LBS_BODY', 'shuffled')
 if os.environ.get('LBS_V'):   # (experiment: another vertex count, e.g. 6912 = 108 x 64: 128-byte-aligned output rows)
     synth.MODEL_DIMS = dict(synth.MODEL_DIMS); synth.MODEL_DIMS[mt] = (int(os.environ['LBS_V']), synth.MODEL_DIMS[mt][1])
-job = workload.make_job(mt, 8, M, seed=1000, optimize_fingers=(mt == 'mano'), dd=synth.synth_model(mt, seed=1000, vertex_order=order))
+if E_SHAPE:
+    dd = dict(synth.synth_model(mt, seed=1000, vertex_order=order, num_betas=16 + E_SHAPE))
+    sd = np.array(dd['shapedirs'], dtype=np.float64)
+    sd[:, :, 16:] *= 0.01 / np.maximum(np.abs(sd[:, :, 16:]).max(axis=(0, 1), keepdims=True), 1e-12)
+    dd['shapedirs'] = sd
+    job = workload.make_job(mt, 8, M, seed=1000, optimize_fingers=(mt == 'mano'), dd=dd, num_betas=16 + E_SHAPE)
+else:
+    job = workload.make_job(mt, 8, M, seed=1000, optimize_fingers=(mt == 'mano'), dd=synth.synth_model(mt, seed=1000, vertex_order=order))
 solver = workload.make_solver(job)
+if E_SHAPE:
+    solver.dev.set_free_shape(16, E_SHAPE)
 sm = job['sm']
 dev = torch.device('cuda', 0)
 rng = np.random.default_rng(0)
@@ -26,22 +48,29 @@ pose = torch.from_numpy(pose_h).to(dev)
 trans = torch.from_numpy(rng.normal(0, 1, (F, 3)).astype(np.float32)).to(dev)
 verts = torch.empty((F, sm.V, 3), dtype=torch.float32, device=dev)
 stream = torch.cuda.current_stream().cuda_stream
-run = lambda: solver.dev.lbs_forward_device(F, pose.data_ptr(), trans.data_ptr(), verts.data_ptr(), C.c_void_p(stream))
+shape_h = rng.normal(0, 1, (F, max(E_SHAPE, 1))).astype(np.float32)
+shape = torch.from_numpy(shape_h).to(dev)
+if E_SHAPE:
+    run = lambda: solver.dev.lbs_forward_device(F, pose.data_ptr(), trans.data_ptr(), verts.data_ptr(), C.c_void_p(stream), shape_ptr=shape.data_ptr())
+else:
+    run = lambda: solver.dev.lbs_forward_device(F, pose.data_ptr(), trans.data_ptr(), verts.data_ptr(), C.c_void_p(stream))
 for _ in range(3):
     run()
 torch.cuda.synchronize()
-e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-e0.record()
-for _ in range(reps):
-    run()
-e1.record()
-torch.cuda.synchronize()
-t = e0.elapsed_time(e1) * 1e-3 / reps
 out_bytes = F * sm.V * 12
-print(f'{mt} [{order} vertex order{", still hands" if os.environ.get("LBS_HANDS") == "still" else ""}] F={F}: {t*1e6:.1f} us per call, output {out_bytes/1e6:.1f} MB -> {out_bytes/t/1e9:.0f} GB/s ({out_bytes/t/8e12*100:.1f}% of 8 TB/s), {F/t:.0f} frames/s')
+for _ in range(REPEATS):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        run()
+    e1.record()
+    torch.cuda.synchronize()
+    t = e0.elapsed_time(e1) * 1e-3 / reps
+    print(f'{mt} [{order} vertex order{", still hands" if os.environ.get("LBS_HANDS") == "still" else ""}{f", {E_SHAPE} shape coefficients" if E_SHAPE else ""}] F={F}: {t*1e6:.1f} us per call, output {out_bytes/1e6:.1f} MB -> {out_bytes/t/1e9:.0f} GB/s ({out_bytes/t/8e12*100:.1f}% of 8 TB/s), {F/t:.0f} frames/s')
 
 if os.environ.get('LBS_CHECK'):
-    ref = solver.dev.lbs_forward(pose[:40].cpu().numpy().astype(np.float64), trans[:40].cpu().numpy().astype(np.float64))
+    ref = solver.dev.lbs_forward(pose[:40].cpu().numpy().astype(np.float64), trans[:40].cpu().numpy().astype(np.float64),
+                                 shape=shape_h[:40].astype(np.float64) if E_SHAPE else None)
     got = verts[:40].cpu().numpy()
     print(f'  check vs the f64 kernel on 40 frames: max |diff| {np.abs(got - ref).max():.2e} m')
 if int(os.environ.get('MOSHII_LBS_STOP', '0')) & 16:

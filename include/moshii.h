@@ -72,7 +72,9 @@ typedef struct moshii_attach_s* moshii_attach_t;  /* marker attachment: compact 
 const char* moshii_last_error(void);
 /* 100: round 1-2 ABI.  101: moshii_stagei_desc grew by the trailing output pointer `init_sq` -- the struct carries no size field, so a
  * caller built against the 100 header must not call a 101 library's moshii_stagei_solve (it would read past the caller's struct);
- * check moshii_version() >= 101 before filling a moshii_stagei_desc declared from this header, and zero the struct first. */
+ * check moshii_version() >= 101 before filling a moshii_stagei_desc declared from this header, and zero the struct first.
+ * 102: moshii_solve_opts grew by the joint-angle term.  103: moshii_lbs_forward_shape_*.  104: moshii_model_set_faces,
+ * moshii_vertex_normals_*, moshii_virtual_markers_* (new calls only: no struct changed). */
 int  moshii_version(void);
 /* first 16 hex digits of the SHA-256 over the sources this binary was compiled from (python -m moshpp_amd.build computes the same
  * over the tree: a stale binary is detectable); "unknown" for a build outside build.py */
@@ -150,6 +152,43 @@ int moshii_lbs_forward_shape_f64(moshii_model_t m, int32_t F, const double* pose
                                  double* verts, uint32_t flags, void* stream);
 int moshii_lbs_forward_shape_f32(moshii_model_t m, int32_t F, const float* pose, const float* trans, const float* shape,
                                  float* verts, uint32_t flags, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The mesh as a surface (version 104): triangles on the model handle, vertex normals of exported meshes, virtual markers.
+ * ------------------------------------------------------------------------------------------- */
+
+/* faces[n_faces][3] (host; can_model.f): validated (an id outside [0, V) is MOSHII_ERR_ARG) and turned into a vertex ->
+ * incident-corner table on the device -- per vertex v and incident face the two other vertices (p, q) in the face's cyclic order, so
+ * that (p - v) x (q - v) is the face's scaled normal; 16-bit pairs while V <= 65 535.  A face that names a vertex twice contributes
+ * nothing, a vertex without faces gets an empty row.  n_faces = 0 clears the table, another call replaces it.  Nothing else on the
+ * handle changes: a handle that never sees this call behaves exactly as before. */
+int moshii_model_set_faces(moshii_model_t m, int32_t n_faces, const int32_t* faces);
+
+/* Area-weighted vertex normals of F given meshes: verts[F][V][3] -> normals[F][V][3].  The reference's VertNormals(normalized=True)
+ * (src/moshpp/models/ch_vert_normals.py, == psbody Mesh.estimate_vertex_normals): the unnormalised cross products of the incident
+ * faces summed and divided by the length of the sum; a zero sum and a vertex without faces give (0, 0, 0).
+ * _f32 accumulates in f64 from its f32 inputs and rounds once on the store (|error| <= 2^-24 per component against f64 arithmetic on
+ * the same f32 vertices); a workgroup stages whole frames in LDS; frames beyond the LDS budget, and MOSHII_VN_KERNEL=gather in the
+ * environment, take the kernel that gathers neighbours through L2, which _f64 always uses.
+ * Buffers host or device per flags; asynchronous on `stream` with MOSHII_BUFFERS_DEVICE.  Any F (64-bit addressing throughout).
+ * Before moshii_model_set_faces: MOSHII_ERR_ARG. */
+int moshii_vertex_normals_f32(moshii_model_t m, int32_t F, const float* verts, float* normals, uint32_t flags, void* stream);
+int moshii_vertex_normals_f64(moshii_model_t m, int32_t F, const double* verts, double* normals, uint32_t flags, void* stream);
+
+/* Virtual markers of F solved frames: markers[f][i] = verts_f[vids[i]] + dist[i] * normal_f[vids[i]] -- the rule by which the
+ * reference places a marker on ONE canonical body (prepare_mosh_markers_latent, src/moshpp/chmosh.py:57-67; marker_layout_as_mesh /
+ * marker_layout_to_c3d, src/moshpp/marker_layout/edit_tools.py:288-416), applied to every frame.  verts_f is what the matching
+ * moshii_lbs_forward[_shape]_f32 / _f64 call computes (the same kernels); shape as there (NULL: the plain export; non-null without a
+ * declared block: MOSHII_ERR_ARG).  vids[M] and dist[M] (metres; zero and negative allowed, vids may repeat) are HOST arrays;
+ * pose / trans / shape / markers[F][M][3] / marker_normals[F][M][3] (or NULL) live where flags say.  The full meshes exist only in
+ * scratch the handle owns, a batch of frames at a time (256 MB by default; MOSHII_VM_BATCH=<frames> in the environment overrides
+ * it): F x M x 3 values are all that reaches the caller.  One call per handle at a time. */
+int moshii_virtual_markers_f32(moshii_model_t m, int32_t F, const float* pose, const float* trans, const float* shape /* or NULL */,
+                               int32_t M, const int32_t* vids, const float* dist, float* markers, float* marker_normals,
+                               uint32_t flags, void* stream);
+int moshii_virtual_markers_f64(moshii_model_t m, int32_t F, const double* pose, const double* trans, const double* shape /* or NULL */,
+                               int32_t M, const int32_t* vids, const double* dist, double* markers, double* marker_normals,
+                               uint32_t flags, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Pose prior.  Replaces create_gmm_body_prior / MaxMixtureComplete
@@ -385,7 +424,8 @@ typedef struct moshii_stagei_desc {
 
 int moshii_stagei_solve(moshii_model_t m, moshii_prior_t prior /* may be NULL */, const moshii_stagei_desc* desc, void* stream);
 
-/* Introspection for benchmarks: name and dynamic-LDS bytes of the kernel the last moshii_chain_solve used. */
+/* Introspection for benchmarks and tests: name, dynamic-LDS bytes and workgroup size of the kernel the last moshii_chain_solve or
+ * moshii_vertex_normals_* call launched ("k_vn_lds", "k_vn_gather<float>", "k_vn_gather<double>" for the latter). */
 int moshii_last_launch_info(char* kernel_name, int32_t name_cap, int32_t* lds_bytes, int32_t* block_threads);
 
 #ifdef __cplusplus

@@ -90,6 +90,13 @@ EXPORTS = {
     'moshii_lbs_forward_f32': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     'moshii_lbs_forward_shape_f64': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     'moshii_lbs_forward_shape_f32': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    'moshii_model_set_faces': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    'moshii_vertex_normals_f32': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    'moshii_vertex_normals_f64': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    'moshii_virtual_markers_f32': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    'moshii_virtual_markers_f64': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     'moshii_prior_create': (C.c_int, [C.c_int32, C.c_int32, _c_double_p, _c_double_p, _c_double_p, C.POINTER(C.c_void_p)]),
     'moshii_prior_destroy': (C.c_int, [C.c_void_p]),
     'moshii_attach_create': (C.c_int, [C.c_void_p, C.c_int32, _c_int_p, _c_double_p, C.POINTER(C.c_void_p)]),
@@ -101,6 +108,13 @@ EXPORTS = {
     'moshii_sequence_solve': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SolveOpts), C.c_int32, C.POINTER(SequenceDesc),
                                         C.POINTER(ChunkOpts), C.c_uint32, C.c_void_p, C.POINTER(ChunkReport)]),
     'moshii_last_launch_info': (C.c_int, [C.c_char_p, C.c_int32, _c_int_p, _c_int_p]),
+}
+
+# exported by the library, not part of the C ABI of include/moshii.h: device buffers for DeviceBuffer below
+_INTERNAL = {
+    'moshii_internal_dev_alloc': (C.c_void_p, [C.c_size_t]),
+    'moshii_internal_dev_free': (None, [C.c_void_p]),
+    'moshii_internal_dev_copy': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
 }
 
 _lib = None
@@ -119,7 +133,7 @@ def load():
         raise MoshiiError(f'{LIB_PATH} not found: build it with `python -m moshpp_amd.build` '
                           f'(there is no CPU fallback for the Stage-II path)')
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in EXPORTS.items():
+    for name, (res, args) in list(EXPORTS.items()) + list(_INTERNAL.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -157,6 +171,40 @@ def _dp(a):
 
 def _ip(a):
     return a.ctypes.data_as(_c_int_p)
+
+
+class DeviceBuffer:
+    """A device allocation of the library's own (for callers that chain device-buffer calls without another allocator)."""
+
+    def __init__(self, nbytes):
+        lib = load()
+        self.nbytes = int(nbytes)
+        self.ptr = lib.moshii_internal_dev_alloc(self.nbytes)
+        if not self.ptr:
+            raise MoshiiError(f'device allocation of {self.nbytes} bytes failed')
+
+    def upload(self, a):
+        a = np.ascontiguousarray(a)
+        assert a.nbytes <= self.nbytes
+        if load().moshii_internal_dev_copy(self.ptr, a.ctypes.data, a.nbytes, 1):
+            raise MoshiiError('host -> device copy failed')
+
+    def download(self, out):
+        assert out.flags.c_contiguous and out.nbytes <= self.nbytes
+        if load().moshii_internal_dev_copy(out.ctypes.data, self.ptr, out.nbytes, 0):
+            raise MoshiiError('device -> host copy failed')
+        return out
+
+    def close(self):
+        if getattr(self, 'ptr', None):
+            load().moshii_internal_dev_free(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Model:
@@ -249,6 +297,119 @@ class Model:
         if not np.isfinite(shape).all():
             raise ValueError('lbs_forward: shape holds non-finite coefficients')
         return shape
+
+    # ---- the mesh as a surface: faces, vertex normals, virtual markers ----
+    def set_faces(self, faces):
+        """Triangles faces[n, 3] (vertex ids) for vertex_normals / virtual_markers; an empty list clears them."""
+        faces = np.asarray(faces)
+        if faces.size == 0:
+            faces = np.zeros((0, 3), dtype=np.int32)
+        if faces.ndim != 2 or faces.shape[1] != 3 or not np.issubdtype(faces.dtype, np.integer):
+            raise ValueError(f'set_faces: faces must be integers [n, 3], got {faces.dtype} {tuple(faces.shape)}')
+        if len(faces) and (faces.min() < 0 or faces.max() >= self.V):
+            raise ValueError(f'set_faces: vertex ids outside [0, {self.V})')
+        faces = np.ascontiguousarray(faces, dtype=np.int32)
+        check(load().moshii_model_set_faces(self.handle, len(faces), faces.ctypes.data if len(faces) else None))
+        self.n_faces = len(faces)
+
+    def _need_faces(self, who):
+        if int(getattr(self, 'n_faces', 0)) <= 0:
+            raise ValueError(f'{who}: the model has no faces (set_faces)')
+
+    def vertex_normals(self, verts):
+        """Area-weighted unit vertex normals [F, V, 3] of the meshes verts[F, V, 3] (or [V, 3]); float32 or float64 as the array."""
+        self._need_faces('vertex_normals')
+        verts = np.asarray(verts)
+        if verts.dtype not in (np.float32, np.float64):
+            raise ValueError(f'vertex_normals: verts must be float32 or float64, not {verts.dtype}')
+        one = verts.ndim == 2
+        v = verts[None] if one else verts
+        if v.ndim != 3 or v.shape[1:] != (self.V, 3):
+            raise ValueError(f'vertex_normals: verts must be [F, {self.V}, 3], got {tuple(verts.shape)}')
+        v = np.ascontiguousarray(v)
+        out = np.zeros_like(v)
+        fn = load().moshii_vertex_normals_f64 if v.dtype == np.float64 else load().moshii_vertex_normals_f32
+        check(fn(self.handle, v.shape[0], v.ctypes.data, out.ctypes.data, BUFFERS_HOST, None))
+        return out[0] if one else out
+
+    def vertex_normals_device(self, F, verts_ptr, normals_ptr, stream=None, f32=True):
+        self._need_faces('vertex_normals_device')
+        fn = load().moshii_vertex_normals_f32 if f32 else load().moshii_vertex_normals_f64
+        check(fn(self.handle, F, verts_ptr, normals_ptr, BUFFERS_DEVICE, stream))
+
+    def _check_markers(self, vids, dist, dtype, who):
+        vids = np.asarray(vids)
+        if vids.ndim != 1 or len(vids) < 1 or not np.issubdtype(vids.dtype, np.integer):
+            raise ValueError(f'{who}: vids must be a non-empty list of integer vertex ids')
+        if vids.min() < 0 or vids.max() >= self.V:
+            raise ValueError(f'{who}: vids outside [0, {self.V})')
+        dist = np.asarray(dist, dtype=np.float64)
+        if dist.ndim == 0:
+            dist = np.full(len(vids), float(dist))
+        if dist.shape != vids.shape or not np.isfinite(dist).all():
+            raise ValueError(f'{who}: dist must be {len(vids)} finite distances (metres)')
+        return np.ascontiguousarray(vids, dtype=np.int32), np.ascontiguousarray(dist, dtype=dtype)
+
+    def virtual_markers(self, pose, trans, vids, dist, dtype=np.float64, shape=None, return_normals=False):
+        """markers[F, M, 3] = verts_f[vids] + dist * vertex normal, frame by frame, for pose variables pose[F, NP], trans[F, 3] (host
+        arrays) -- the meshes never leave the device.  shape as in lbs_forward.  return_normals: (markers, normals[F, M, 3])."""
+        if dtype not in (np.float64, np.float32):
+            raise ValueError(f'virtual_markers: dtype must be numpy float64 or float32, not {dtype!r}')
+        self._need_faces('virtual_markers')
+        vids, dist = self._check_markers(vids, dist, dtype, 'virtual_markers')
+        pose = np.ascontiguousarray(np.atleast_2d(pose), dtype=dtype)
+        trans = np.ascontiguousarray(np.atleast_2d(trans), dtype=dtype)
+        F = pose.shape[0]
+        if pose.shape != (F, self.NP) or trans.shape != (F, 3):
+            raise ValueError(f'virtual_markers: pose / trans must be [F, {self.NP}] / [F, 3], got {pose.shape} / {trans.shape}')
+        if shape is not None:
+            shape = self._check_shape_rows(shape, F, dtype)
+        M = len(vids)
+        out = np.zeros((F, M, 3), dtype=dtype)
+        nrm = np.zeros((F, M, 3), dtype=dtype) if return_normals else None
+        fn = load().moshii_virtual_markers_f64 if dtype == np.float64 else load().moshii_virtual_markers_f32
+        check(fn(self.handle, F, pose.ctypes.data, trans.ctypes.data, shape.ctypes.data if shape is not None else None, M,
+                 vids.ctypes.data, dist.ctypes.data, out.ctypes.data, nrm.ctypes.data if return_normals else None, BUFFERS_HOST, None))
+        return (out, nrm) if return_normals else out
+
+    def virtual_markers_device(self, F, pose_ptr, trans_ptr, vids, dist, out_ptr, normals_ptr=None, stream=None, f32=True, shape_ptr=None):
+        """Device buffers for pose / trans / shape / markers / normals; vids and dist are host arrays."""
+        self._need_faces('virtual_markers_device')
+        vids, dist = self._check_markers(vids, dist, np.float32 if f32 else np.float64, 'virtual_markers_device')
+        fn = load().moshii_virtual_markers_f32 if f32 else load().moshii_virtual_markers_f64
+        check(fn(self.handle, F, pose_ptr, trans_ptr, shape_ptr, len(vids), vids.ctypes.data, dist.ctypes.data, out_ptr, normals_ptr,
+                 BUFFERS_DEVICE, stream))
+
+    def lbs_forward_with_normals(self, pose, trans, dtype=np.float32, shape=None):
+        """(verts, normals), both [F, V, 3]: the export into a device buffer, the normals from that buffer, two copies back -- the
+        vertices do not visit the host in between."""
+        if dtype not in (np.float64, np.float32):
+            raise ValueError(f'lbs_forward_with_normals: dtype must be numpy float64 or float32, not {dtype!r}')
+        self._need_faces('lbs_forward_with_normals')
+        pose = np.ascontiguousarray(np.atleast_2d(pose), dtype=dtype)
+        trans = np.ascontiguousarray(np.atleast_2d(trans), dtype=dtype)
+        F = pose.shape[0]
+        if pose.shape != (F, self.NP) or trans.shape != (F, 3):
+            raise ValueError(f'lbs_forward_with_normals: pose / trans must be [F, {self.NP}] / [F, 3], got {pose.shape} / {trans.shape}')
+        if shape is not None:
+            shape = self._check_shape_rows(shape, F, dtype)
+        verts = np.zeros((F, self.V, 3), dtype=dtype)
+        normals = np.zeros_like(verts)
+        if F == 0:
+            return verts, normals
+        bufs = [DeviceBuffer(a.nbytes) for a in (pose, trans, verts, normals)] + ([DeviceBuffer(shape.nbytes)] if shape is not None else [])
+        try:
+            bufs[0].upload(pose); bufs[1].upload(trans)
+            if shape is not None:
+                bufs[4].upload(shape)
+            f32 = dtype == np.float32
+            self.lbs_forward_device(F, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, None, f32=f32, shape_ptr=bufs[4].ptr if shape is not None else None)
+            self.vertex_normals_device(F, bufs[2].ptr, bufs[3].ptr, None, f32=f32)
+            bufs[2].download(verts); bufs[3].download(normals)      # (blocking copies on the null stream: behind both kernels)
+        finally:
+            for b in bufs:
+                b.close()
+        return verts, normals
 
     def lbs_forward_device(self, F, pose_ptr, trans_ptr, out_ptr, stream=None, f32=True, shape_ptr=None):
         """Device buffers (f32: float, else double).  shape_ptr: [F][nshape] coefficients of the free shape block on the device."""

@@ -233,6 +233,20 @@ class StageIISolver:
                 raise KeyError(f"StageIISolver.vertices: the result has no '{k}'")
         return self.dev.lbs_forward(out['pose'], out['trans'], dtype=dtype, shape=out['shape'] if self.n_shape else None)
 
+    def virtual_markers(self, out, vids, dist, dtype=np.float32, return_normals=False):
+        """markers[F, M, 3] of a solve() result: vertex vids[i] of every solved frame's mesh + dist[i] x its vertex normal (the
+        reference's marker placement rule, chmosh.py:57-67, on every frame) -- on the solver's own handle, the meshes stay on the
+        device.  The surface model needs its triangles `f`."""
+        for k in ('pose', 'trans') + (('shape',) if self.n_shape else ()):
+            if k not in out:
+                raise KeyError(f"StageIISolver.virtual_markers: the result has no '{k}'")
+        if getattr(self.sm, 'f', None) is None:
+            raise ValueError('StageIISolver.virtual_markers: the surface model has no faces (f)')
+        if not getattr(self.dev, 'n_faces', 0):
+            self.dev.set_faces(self.sm.f)
+        return self.dev.virtual_markers(out['pose'], out['trans'], vids, dist, dtype=dtype, shape=out['shape'] if self.n_shape else None,
+                                        return_normals=return_normals)
+
 
 def mosh_stageii(mocap_fname: str, cfg, markers_latent: np.ndarray, latent_labels: list, betas: np.ndarray,
                  marker_meta: dict, v_template_fname=None) -> dict:

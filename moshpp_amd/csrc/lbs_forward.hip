@@ -991,6 +991,143 @@ __global__ __launch_bounds__(256, 2) void k_lbs_export(Lbs32Model lm, int V, int
 #undef LX_STAMP
 }
 
+// ---- vertex normals of exported meshes (moshii_vertex_normals_*, moshii_virtual_markers_*) ----------------------------------------
+// VertNormals(normalized=True) (reference src/moshpp/models/ch_vert_normals.py; psbody estimate_vertex_normals): the unnormalised
+// cross products of a vertex's incident faces summed, divided by the length of the sum; a zero sum gives (0, 0, 0).
+// The faces come as a vertex -> incident-corner table in CSR form (moshii_model_set_faces): rows[v] .. rows[v + 1] index `pairs`, one
+// entry per incident face = the two other vertices (p, q) in the face's cyclic order, so the face's scaled normal is
+// (p - v) x (q - v).  Entries are 16-bit pairs in one dword while V <= 65 535 (W16; SMPL-H: 183 KB, read once per frame, L2
+// resident), two dwords otherwise.
+// Four lanes (a quad) share a vertex: lane `sub` takes corners sub, sub + 4, ... of the row, the partial sums meet through two
+// DPP quad permutes -- valence runs from 5 to 34 on these bodies, and a wave waits for its longest row: a quarter of it this way --
+// and lanes 0 .. 2 of the quad store x, y, z: a wave writes 16 consecutive vertices, 192 contiguous bytes.
+// Arithmetic in VN_ACC_T = double for both precisions (the f32 call converts its inputs and rounds once on the store): f32 cross
+// products lose up to 5.6e-7 on sliver triangles.  (Frame sizes below are those of the released bodies: SMPL-H V = 6 890, SMPL-X
+// V = 10 475; the triangulated synthetic bodies of the tests and of tools/lbs_bench.py --normals are larger: 7 634 / 11 270.)  -DVN_ACC_T=float builds the f32-accumulating kernel for timing comparisons only.
+#ifndef VN_ACC_T
+#define VN_ACC_T double
+#endif
+#define VN_THREADS 1024                 // k_vn_lds: 16 waves = 256 quads
+#define VN_LDS_MAX (160 * 1024 - 256)   // a workgroup's frames in LDS (SMPL-H 82.7 KB, SMPL-X 125.7 KB a frame)
+#define VN_LDS_PAIR (78 * 1024)         // small bodies: as many frames as keep TWO workgroups on a CU (one loads while the other computes)
+
+template <int CTRL>
+__device__ __forceinline__ double vn_dpp(double x) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+template <int CTRL>
+__device__ __forceinline__ float vn_dpp(float x) {
+    int b;
+    __builtin_memcpy(&b, &x, 4);
+    b = __builtin_amdgcn_update_dpp(0, b, CTRL, 0xf, 0xf, false);
+    __builtin_memcpy(&x, &b, 4);
+    return x;
+}
+// sum over the four lanes of a quad, the same bits in all four (quad_perm [1,0,3,2], then [2,3,0,1])
+template <class A>
+__device__ __forceinline__ A vn_quad_sum(A x) {
+    x += vn_dpp<0xB1>(x);
+    x += vn_dpp<0x4E>(x);
+    return x;
+}
+
+// lane `sub` of a quad: its share of vertex v's row on the mesh `fr` ([V][3], LDS or global), summed over the quad and normalised.
+// EVERY lane of the wave calls this (the quad permutes are wave-wide); `valid` = false lanes read nothing.
+template <class A, class T, bool W16>
+__device__ __forceinline__ void vn_vertex(const T* fr, unsigned v, int sub, bool valid, const unsigned* __restrict__ rows,
+                                          const unsigned* __restrict__ pairs, A* n, A* pos) {
+    A sx = 0, sy = 0, sz = 0, vx = 0, vy = 0, vz = 0;
+    if (valid) {
+        const unsigned beg = rows[v], end = rows[v + 1];
+        vx = (A)fr[3 * v]; vy = (A)fr[3 * v + 1]; vz = (A)fr[3 * v + 2];
+        for (unsigned c = beg + sub; c < end; c += 4) {
+            unsigned p, q;
+            if (W16) { const unsigned w = pairs[c]; p = w & 0xffffu; q = w >> 16; }
+            else { p = pairs[2 * (size_t)c]; q = pairs[2 * (size_t)c + 1]; }
+            const A ax = (A)fr[3 * p] - vx, ay = (A)fr[3 * p + 1] - vy, az = (A)fr[3 * p + 2] - vz;
+            const A bx = (A)fr[3 * q] - vx, by = (A)fr[3 * q + 1] - vy, bz = (A)fr[3 * q + 2] - vz;
+            sx += ay * bz - az * by;
+            sy += az * bx - ax * bz;
+            sz += ax * by - ay * bx;
+        }
+    }
+    sx = vn_quad_sum(sx); sy = vn_quad_sum(sy); sz = vn_quad_sum(sz);
+    const A d = sx * sx + sy * sy + sz * sz;
+    const A inv = d > (A)0 ? (A)1 / (A)sqrt((double)d) : (A)0;
+    n[0] = sx * inv; n[1] = sy * inv; n[2] = sz * inv;
+    pos[0] = vx; pos[1] = vy; pos[2] = vz;
+}
+
+// f32 hot path: a workgroup takes G whole frames at a time.  The frames' G x V x 12 bytes go to LDS with 16-byte loads (the LDS copy
+// starts `a` floats in, a = the global address's dword offset within 16 bytes, so that both sides of every 16-byte move are aligned;
+// up to three floats at either end move alone), the quads walk the CSR rows and gather the neighbours from LDS.
+template <bool W16>
+__global__ __launch_bounds__(VN_THREADS) void k_vn_lds(int V, int F, int G, const float* __restrict__ verts, float* __restrict__ normals,
+                                                        const unsigned* __restrict__ rows, const unsigned* __restrict__ pairs) {
+    extern __shared__ __attribute__((aligned(16))) float smf[];
+    const int tid = threadIdx.x, sub = tid & 3;
+    const unsigned fv = (unsigned)V * 3;
+    for (int fb = blockIdx.x * G; fb < F; fb += gridDim.x * G) {
+        const int ng = min(G, F - fb);
+        const float* src = verts + (size_t)fb * fv;
+        const unsigned n = (unsigned)ng * fv;
+        const unsigned a = (unsigned)(((size_t)src >> 2) & 3), head = ((4u - a) & 3u) < n ? ((4u - a) & 3u) : n, n4 = (n - head) >> 2, tail = n - head - 4 * n4;
+        for (unsigned i = tid; i < n4; i += VN_THREADS)
+            *reinterpret_cast<f32x4*>(smf + a + head + 4 * i) = *reinterpret_cast<const f32x4*>(src + head + 4 * i);
+        if ((unsigned)tid < head) smf[a + tid] = src[tid];
+        if ((unsigned)tid < tail) smf[a + head + 4 * n4 + tid] = src[head + 4 * n4 + tid];
+        __syncthreads();
+        for (int fl = 0; fl < ng; ++fl) {
+            const float* fr = smf + a + (unsigned)fl * fv;
+            float* out = normals + (size_t)(fb + fl) * fv;
+            for (unsigned v0 = 0; v0 < (unsigned)V; v0 += VN_THREADS / 4) {
+                const unsigned v = v0 + (tid >> 2);
+                VN_ACC_T nr[3], pos[3];
+                vn_vertex<VN_ACC_T, float, W16>(fr, v, sub, v < (unsigned)V, rows, pairs, nr, pos);
+                if (v < (unsigned)V && sub < 3) out[3 * v + sub] = (float)(sub == 0 ? nr[0] : sub == 1 ? nr[1] : nr[2]);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// The same rows with the neighbours gathered through L2: the f64 call (an f64 SMPL-H frame is 165 KB), f32 frames beyond the LDS
+// budget, MOSHII_VN_KERNEL=gather.  A workgroup = 64 consecutive vertices, walked over the frames blockIdx.y, + gridDim.y, ...
+template <class T, bool W16>
+__global__ __launch_bounds__(256) void k_vn_gather(int V, int F, const T* __restrict__ verts, T* __restrict__ normals,
+                                                    const unsigned* __restrict__ rows, const unsigned* __restrict__ pairs) {
+    typedef typename std::conditional<std::is_same<T, double>::value, double, VN_ACC_T>::type A;
+    const int tid = threadIdx.x, sub = tid & 3;
+    const unsigned fv = (unsigned)V * 3, v = blockIdx.x * 64 + (tid >> 2);
+    for (int f = blockIdx.y; f < F; f += gridDim.y) {
+        A nr[3], pos[3];
+        vn_vertex<A, T, W16>(verts + (size_t)f * fv, v, sub, v < (unsigned)V, rows, pairs, nr, pos);
+        if (v < (unsigned)V && sub < 3) normals[(size_t)f * fv + 3 * v + sub] = (T)(sub == 0 ? nr[0] : sub == 1 ? nr[1] : nr[2]);
+    }
+}
+
+// Virtual markers of a batch of meshes: marker i of frame f = verts[f][vids[i]] + dist[i] x its vertex normal -- the reference's
+// prepare_mosh_markers_latent (src/moshpp/chmosh.py:57-67) on every frame.  One quad per (frame, marker), f64 arithmetic in both
+// precisions; only the M rows of the marker vertices are walked.
+template <class T, bool W16>
+__global__ __launch_bounds__(256) void k_vn_markers(int V, int nf, int M, const T* __restrict__ verts, const int* __restrict__ vids,
+                                                     const double* __restrict__ dist, T* __restrict__ markers, T* __restrict__ mnormals,
+                                                     const unsigned* __restrict__ rows, const unsigned* __restrict__ pairs) {
+    const int tid = threadIdx.x, sub = tid & 3;
+    const unsigned total = (unsigned)nf * (unsigned)M, item = blockIdx.x * 64 + (tid >> 2);
+    const bool valid = item < total;
+    const unsigned f = valid ? item / (unsigned)M : 0, i = valid ? item - f * (unsigned)M : 0;
+    double nr[3], pos[3];
+    vn_vertex<double, T, W16>(verts + (size_t)f * V * 3, valid ? (unsigned)vids[i] : 0u, sub, valid, rows, pairs, nr, pos);
+    if (valid && sub < 3) {
+        const double nc = sub == 0 ? nr[0] : sub == 1 ? nr[1] : nr[2], pc = sub == 0 ? pos[0] : sub == 1 ? pos[1] : pos[2];
+        markers[(size_t)item * 3 + sub] = (T)(pc + dist[i] * nc);
+        if (mnormals) mnormals[(size_t)item * 3 + sub] = (T)nc;
+    }
+}
+
 }  // namespace
 
 static void free_ptr(void* p) { if (p) hipFree(p); }
@@ -1333,5 +1470,69 @@ extern "C" hipError_t moshii_launch_lbs_f32(hipStream_t stream, const ModelDev* 
     if (e != hipSuccess) return e;
     if (sh) hipLaunchKernelGGL(k_lbs_export<true>, dim3(8 * nslots), dim3(256), LX_LDS_BYTES, stream, lm, md->V, F, NVT, NFT, verts, lm.varflag, lm.epoch, lm.dbgbuf, dbg);
     else hipLaunchKernelGGL(k_lbs_export<false>, dim3(8 * nslots), dim3(256), LX_LDS_BYTES, stream, lm, md->V, F, NVT, NFT, verts, lm.varflag, lm.epoch, lm.dbgbuf, dbg);
+    return hipGetLastError();
+}
+
+// ---- vertex normals / virtual markers: launches (the handle, its face table and the checks live in moshii_api.hip) ----
+// All addressing is 64-bit per frame (no buffer resources): any F runs in one call, the gather kernel walks frames beyond its grid.
+// *which (may be null): the kernel taken, *lds_bytes / *threads its dynamic LDS and workgroup size (moshii_last_launch_info)
+extern "C" hipError_t moshii_launch_vertex_normals(hipStream_t stream, int V, int F, int f64, const void* verts, void* normals,
+                                                   const unsigned* rows, const unsigned* pairs, int w16, const char** which,
+                                                   int* lds_bytes, int* threads) {
+    const char* none = nullptr;
+    int i0 = 0, i1 = 0;
+    if (!which) which = &none;
+    if (!lds_bytes) lds_bytes = &i0;
+    if (!threads) threads = &i1;
+    *which = ""; *lds_bytes = 0; *threads = 256;
+    if (F <= 0 || V <= 0) return hipSuccess;
+    const dim3 ggrid((V + 63) / 64, std::min(F, 1024));
+    if (f64) {
+        *which = "k_vn_gather<double>";
+        if (w16) hipLaunchKernelGGL((k_vn_gather<double, true>), ggrid, dim3(256), 0, stream, V, F, (const double*)verts, (double*)normals, rows, pairs);
+        else hipLaunchKernelGGL((k_vn_gather<double, false>), ggrid, dim3(256), 0, stream, V, F, (const double*)verts, (double*)normals, rows, pairs);
+        return hipGetLastError();
+    }
+    const char* ek = getenv("MOSHII_VN_KERNEL");   // "gather": the L2 kernel for the f32 call too (tests, tools/lbs_bench.py --normals)
+    const size_t frame = (size_t)V * 12;
+    if ((ek && !strcmp(ek, "gather")) || frame + 16 > VN_LDS_MAX) {
+        *which = "k_vn_gather<float>";
+        if (w16) hipLaunchKernelGGL((k_vn_gather<float, true>), ggrid, dim3(256), 0, stream, V, F, (const float*)verts, (float*)normals, rows, pairs);
+        else hipLaunchKernelGGL((k_vn_gather<float, false>), ggrid, dim3(256), 0, stream, V, F, (const float*)verts, (float*)normals, rows, pairs);
+        return hipGetLastError();
+    }
+    int ncu = 0, devid = 0;
+    hipGetDevice(&devid);
+    hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, devid);
+    if (ncu <= 0) ncu = 256;
+    // frames a workgroup keeps resident: a big body one (a CU holds one workgroup), a small body as many as leave room for a second
+    // workgroup on the CU, but no more than spread the call over every CU twice
+    int G = 1;
+    if (frame + 16 <= VN_LDS_PAIR) G = (int)std::max<size_t>(1, std::min<size_t>((VN_LDS_PAIR - 16) / frame, ((size_t)F + 2 * ncu - 1) / (2 * ncu)));
+    const size_t lds = (((size_t)G * V * 3 + 3) * sizeof(float) + 15) & ~(size_t)15;
+    const int per_cu = lds <= VN_LDS_PAIR ? 2 : 1;
+    const int grid = (int)std::min<long long>(((long long)F + G - 1) / G, (long long)per_cu * ncu);
+    *which = "k_vn_lds"; *lds_bytes = (int)lds; *threads = VN_THREADS;
+    const void* kern = w16 ? reinterpret_cast<const void*>(k_vn_lds<true>) : reinterpret_cast<const void*>(k_vn_lds<false>);
+    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);   // (the opt-in above 64 KB)
+    if (e != hipSuccess) return e;
+    if (w16) hipLaunchKernelGGL(k_vn_lds<true>, dim3(grid), dim3(VN_THREADS), lds, stream, V, F, G, (const float*)verts, (float*)normals, rows, pairs);
+    else hipLaunchKernelGGL(k_vn_lds<false>, dim3(grid), dim3(VN_THREADS), lds, stream, V, F, G, (const float*)verts, (float*)normals, rows, pairs);
+    return hipGetLastError();
+}
+
+// markers[nf][M][3] (and mnormals, or null) of the meshes verts[nf][V][3]; vids / dist on the device
+extern "C" hipError_t moshii_launch_marker_normals(hipStream_t stream, int V, int nf, int M, int f64, const void* verts, const int* vids,
+                                                   const double* dist, void* markers, void* mnormals, const unsigned* rows,
+                                                   const unsigned* pairs, int w16) {
+    if (nf <= 0 || M <= 0) return hipSuccess;
+    const dim3 grid((unsigned)(((long long)nf * M + 63) / 64));
+    if (f64) {
+        if (w16) hipLaunchKernelGGL((k_vn_markers<double, true>), grid, dim3(256), 0, stream, V, nf, M, (const double*)verts, vids, dist, (double*)markers, (double*)mnormals, rows, pairs);
+        else hipLaunchKernelGGL((k_vn_markers<double, false>), grid, dim3(256), 0, stream, V, nf, M, (const double*)verts, vids, dist, (double*)markers, (double*)mnormals, rows, pairs);
+    } else {
+        if (w16) hipLaunchKernelGGL((k_vn_markers<float, true>), grid, dim3(256), 0, stream, V, nf, M, (const float*)verts, vids, dist, (float*)markers, (float*)mnormals, rows, pairs);
+        else hipLaunchKernelGGL((k_vn_markers<float, false>), grid, dim3(256), 0, stream, V, nf, M, (const float*)verts, vids, dist, (float*)markers, (float*)mnormals, rows, pairs);
+    }
     return hipGetLastError();
 }

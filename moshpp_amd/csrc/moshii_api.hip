@@ -20,6 +20,12 @@ extern "C" hipError_t moshii_launch_markers(int F, size_t lds_bytes, hipStream_t
                                             const double* trans, double* out);
 extern "C" hipError_t moshii_launch_lbs_f32(hipStream_t stream, const ModelDev* md, int F, const float* pose,
                                             const float* trans, const float* shape, float* verts, void* lbs32);
+extern "C" hipError_t moshii_launch_vertex_normals(hipStream_t stream, int V, int F, int f64, const void* verts, void* normals,
+                                                   const unsigned* rows, const unsigned* pairs, int w16, const char** which,
+                                                   int* lds_bytes, int* threads);
+extern "C" hipError_t moshii_launch_marker_normals(hipStream_t stream, int V, int nf, int M, int f64, const void* verts, const int* vids,
+                                                   const double* dist, void* markers, void* mnormals, const unsigned* rows,
+                                                   const unsigned* pairs, int w16);
 
 namespace {
 
@@ -79,6 +85,10 @@ struct moshii_model_s {
     Lbs32Model l32 = {};
     bool l32_valid = false;
     Scratch scratch;
+    // moshii_model_set_faces: vertex -> incident-corner table (CSR; lbs_forward.hip, "vertex normals"); null = no faces
+    unsigned *d_vn_rows = nullptr, *d_vn_pairs = nullptr;
+    int vn_w16 = 0;
+    Scratch vmscratch;                  // moshii_virtual_markers_*: a batch of full meshes + the marker ids and distances
     ModelDev dev() const {
         ModelDev md;
         md.V = V; md.K = K; md.P = P; md.NP = NP; md.body_dof = body_dof; md.hand_dof = hand_dof;
@@ -354,7 +364,7 @@ struct LaunchInfo { std::string name; int lds = 0; int threads = 0; } g_last;
 extern "C" {
 
 const char* moshii_last_error(void) { return g_err.c_str(); }
-int moshii_version(void) { return 103; }   // 101: moshii_stagei_desc grew by init_sq; 102: moshii_solve_opts by the joint-angle term; 103: moshii_lbs_forward_shape_* (include/moshii.h)
+int moshii_version(void) { return 104; }   // 101: moshii_stagei_desc grew by init_sq; 102: moshii_solve_opts by the joint-angle term; 103: moshii_lbs_forward_shape_*; 104: moshii_model_set_faces, moshii_vertex_normals_*, moshii_virtual_markers_* (include/moshii.h)
 #ifndef MOSHII_SRC_HASH
 #define MOSHII_SRC_HASH "unknown"
 #endif
@@ -460,6 +470,8 @@ int moshii_model_destroy(moshii_model_t m) {
     void* ptrs[] = {m->d_vt, m->d_shapedirs, m->d_posedirs, m->d_weights, m->d_Jreg, m->d_vsh, m->d_J, m->d_hands_mean,
                     m->d_comps, m->d_parents, m->d_depth, m->d_comp_lo, m->d_comp_hi, m->d_col_lo, m->d_col_hi, m->d_anc, m->d_JS};
     for (void* p : ptrs) if (p) hipFree(p);
+    if (m->d_vn_rows) hipFree(m->d_vn_rows);
+    if (m->d_vn_pairs) hipFree(m->d_vn_pairs);
     free_l32(m);
     delete m;
     return MOSHII_OK;
@@ -503,6 +515,20 @@ int moshii_model_get_joints(moshii_model_t m, double* J_out) {
     return MOSHII_OK;
 }
 
+// the f64 export's launch: shape = per-frame coefficients of the free block on the device, or null
+static void launch_lbs_f64(moshii_model_t m, int F, const double* d_pose, const double* d_trans, const double* d_shape, double* d_out,
+                           hipStream_t stream) {
+    if (d_shape) {
+        const size_t lds = (size_t)(m->P + m->K * 33) * sizeof(double);
+        hipLaunchKernelGGL(k_lbs_f64<true>, dim3((m->V + 255) / 256, F), dim3(256), lds, stream, m->dev(), m->d_vsh, m->d_posedirs,
+                           m->d_weights, d_pose, d_trans, d_out, m->d_shapedirs, m->NB, m->shape_start, d_shape);
+    } else {
+        const size_t lds = (size_t)(m->P + m->K * 30) * sizeof(double);
+        hipLaunchKernelGGL(k_lbs_f64<false>, dim3((m->V + 255) / 256, F), dim3(256), lds, stream, m->dev(), m->d_vsh, m->d_posedirs,
+                           m->d_weights, d_pose, d_trans, d_out, (const double*)nullptr, 0, 0, (const double*)nullptr);
+    }
+}
+
 // shape: per-frame coefficients of the free block [F][nshape], or null (the frozen body)
 static int lbs_forward_f64_impl(moshii_model_t m, int32_t F, const double* pose, const double* trans, const double* shape, double* verts,
                                 uint32_t flags, void* stream_) {
@@ -523,15 +549,7 @@ static int lbs_forward_f64_impl(moshii_model_t m, int32_t F, const double* pose,
         d_pose = t_pose; d_trans = t_trans; d_out = t_out;
         if (shape) d_shape = t_shape;
     }
-    if (d_shape) {
-        const size_t lds = (size_t)(m->P + m->K * 33) * sizeof(double);
-        hipLaunchKernelGGL(k_lbs_f64<true>, dim3((m->V + 255) / 256, F), dim3(256), lds, stream, m->dev(), m->d_vsh, m->d_posedirs,
-                           m->d_weights, d_pose, d_trans, d_out, m->d_shapedirs, m->NB, m->shape_start, d_shape);
-    } else {
-        const size_t lds = (size_t)(m->P + m->K * 30) * sizeof(double);
-        hipLaunchKernelGGL(k_lbs_f64<false>, dim3((m->V + 255) / 256, F), dim3(256), lds, stream, m->dev(), m->d_vsh, m->d_posedirs,
-                           m->d_weights, d_pose, d_trans, d_out, (const double*)nullptr, 0, 0, (const double*)nullptr);
-    }
+    launch_lbs_f64(m, F, d_pose, d_trans, d_shape, d_out, stream);
     HIP_TRY(hipGetLastError());
     if (!dev) {
         HIP_TRY(hipStreamSynchronize(stream));
@@ -594,6 +612,179 @@ int moshii_lbs_forward_f32(moshii_model_t m, int32_t F, const float* pose, const
 int moshii_lbs_forward_shape_f32(moshii_model_t m, int32_t F, const float* pose, const float* trans, const float* shape,
                                  float* verts, uint32_t flags, void* stream) {
     return lbs_forward_f32_impl(m, F, pose, trans, shape, verts, flags, stream);
+}
+
+// ---- faces, vertex normals, virtual markers (version 104) ----
+int moshii_model_set_faces(moshii_model_t m, int32_t n_faces, const int32_t* faces) {
+    if (!m || n_faces < 0 || (n_faces > 0 && !faces)) return fail(MOSHII_ERR_ARG, "moshii_model_set_faces: bad argument");
+    if (n_faces > 0x3fffffff) return fail(MOSHII_ERR_UNSUPPORTED, "moshii_model_set_faces: at most 2^30 - 1 faces (32-bit row offsets)");
+    const int V = m->V;
+    for (size_t i = 0; i < (size_t)n_faces * 3; ++i)
+        if (faces[i] < 0 || faces[i] >= V) return fail(MOSHII_ERR_ARG, "moshii_model_set_faces: vertex id outside [0, V)");
+    HIP_TRY(hipDeviceSynchronize());
+    if (m->d_vn_rows) { hipFree(m->d_vn_rows); m->d_vn_rows = nullptr; }
+    if (m->d_vn_pairs) { hipFree(m->d_vn_pairs); m->d_vn_pairs = nullptr; }
+    if (n_faces == 0) return MOSHII_OK;
+    // vertex -> incident corners: for vertex v of face (a, b, c) the other two in cyclic order, (p - v) x (q - v) = the face's scaled
+    // normal; a face that names a vertex twice has none and is left out
+    std::vector<unsigned> rows((size_t)V + 1, 0u);
+    auto good = [&](int f) { const int32_t* t = faces + (size_t)f * 3; return t[0] != t[1] && t[1] != t[2] && t[0] != t[2]; };
+    for (int f = 0; f < n_faces; ++f) if (good(f)) for (int c = 0; c < 3; ++c) ++rows[(size_t)faces[(size_t)f * 3 + c] + 1];
+    for (int v = 0; v < V; ++v) rows[v + 1] += rows[v];
+    const size_t nc = rows[V];
+    const bool w16 = V <= 65535;        // 16-bit pairs: half the table, and every frame reads all of it
+    std::vector<unsigned> pairs(std::max<size_t>(nc * (w16 ? 1 : 2), 1), 0u), fill(rows.begin(), rows.end() - 1);
+    for (int f = 0; f < n_faces; ++f) {
+        if (!good(f)) continue;
+        const int32_t* t = faces + (size_t)f * 3;
+        for (int c = 0; c < 3; ++c) {
+            const unsigned p = (unsigned)t[(c + 1) % 3], q = (unsigned)t[(c + 2) % 3];
+            const size_t at = fill[t[c]]++;
+            if (w16) pairs[at] = p | (q << 16);
+            else { pairs[2 * at] = p; pairs[2 * at + 1] = q; }
+        }
+    }
+    // both parts uploaded before either is published: a failure leaves the handle without a table, never with half of one
+    unsigned *d_rows = nullptr, *d_pairs = nullptr;
+    int rc;
+    if ((rc = dev_upload(rows.data(), rows.size(), &d_rows))) return rc;
+    if ((rc = dev_upload(pairs.data(), pairs.size(), &d_pairs))) { hipFree(d_rows); return rc; }
+    m->d_vn_rows = d_rows; m->d_vn_pairs = d_pairs;
+    m->vn_w16 = w16 ? 1 : 0;
+    return MOSHII_OK;
+}
+
+}  // extern "C"
+
+namespace {
+struct DevTemps {   // device temporaries of a host-buffer call: freed on every way out
+    std::vector<void*> ptrs;
+    template <class T> T* keep(T* p) { ptrs.push_back((void*)p); return p; }
+    ~DevTemps() { for (void* p : ptrs) if (p) hipFree(p); }
+};
+}  // namespace
+
+template <class T>
+static int vertex_normals_impl(moshii_model_t m, int32_t F, const T* verts, T* normals, uint32_t flags, void* stream_, const char* name) {
+    if (!m || !verts || !normals || F < 0) return fail(MOSHII_ERR_ARG, std::string(name) + ": bad argument");
+    if (!m->d_vn_rows) return fail(MOSHII_ERR_ARG, std::string(name) + ": the model has no faces: call moshii_model_set_faces first");
+    if (F == 0) return MOSHII_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    const bool dev = (flags & MOSHII_BUFFERS_DEVICE) != 0;
+    const size_t n = (size_t)F * m->V * 3;
+    const T* d_in = verts;
+    T *d_out = normals, *t_in = nullptr, *t_out = nullptr;
+    DevTemps temps;
+    if (!dev) {
+        int rc = dev_upload(verts, n, &t_in);
+        temps.keep(t_in);
+        if (rc) return rc;
+        HIP_TRY(hipMalloc((void**)&t_out, n * sizeof(T)));
+        temps.keep(t_out);
+        d_in = t_in; d_out = t_out;
+    }
+    const char* which = "";
+    int lds = 0, threads = 0;
+    HIP_TRY(moshii_launch_vertex_normals(stream, m->V, F, sizeof(T) == 8, d_in, d_out, m->d_vn_rows, m->d_vn_pairs, m->vn_w16, &which, &lds, &threads));
+    g_last.name = which; g_last.lds = lds; g_last.threads = threads;
+    if (!dev) {
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemcpy(normals, t_out, n * sizeof(T), hipMemcpyDeviceToHost));
+    }
+    return MOSHII_OK;
+}
+
+extern "C" {
+
+int moshii_vertex_normals_f32(moshii_model_t m, int32_t F, const float* verts, float* normals, uint32_t flags, void* stream) {
+    return vertex_normals_impl(m, F, verts, normals, flags, stream, "moshii_vertex_normals_f32");
+}
+int moshii_vertex_normals_f64(moshii_model_t m, int32_t F, const double* verts, double* normals, uint32_t flags, void* stream) {
+    return vertex_normals_impl(m, F, verts, normals, flags, stream, "moshii_vertex_normals_f64");
+}
+
+}  // extern "C"
+
+static hipError_t export_batch(moshii_model_t m, int nf, const float* pose, const float* trans, const float* shape, float* out, hipStream_t stream) {
+    ModelDev md = m->dev();
+    return moshii_launch_lbs_f32(stream, &md, nf, pose, trans, shape, out, &m->l32);
+}
+static hipError_t export_batch(moshii_model_t m, int nf, const double* pose, const double* trans, const double* shape, double* out, hipStream_t stream) {
+    launch_lbs_f64(m, nf, pose, trans, shape, out, stream);
+    return hipGetLastError();
+}
+
+// The meshes exist only in the handle's scratch, a batch of frames at a time: export (the kernels of moshii_lbs_forward[_shape]_*, so
+// the same vertices bit for bit as that call gives for the batch's frames), then the normals of the M marker vertices alone.
+template <class T>
+static int virtual_markers_impl(moshii_model_t m, int32_t F, const T* pose, const T* trans, const T* shape, int32_t M, const int32_t* vids,
+                                const T* dist, T* markers, T* mnormals, uint32_t flags, void* stream_, const char* name) {
+    if (!m || !pose || !trans || !vids || !dist || !markers || F < 0 || M < 1) return fail(MOSHII_ERR_ARG, std::string(name) + ": bad argument");
+    if (shape && m->nshape == 0) return fail(MOSHII_ERR_ARG, "shape coefficients without a block: call moshii_model_set_free_shape first");
+    if (!m->d_vn_rows) return fail(MOSHII_ERR_ARG, std::string(name) + ": the model has no faces: call moshii_model_set_faces first");
+    for (int i = 0; i < M; ++i) if (vids[i] < 0 || vids[i] >= m->V) return fail(MOSHII_ERR_ARG, std::string(name) + ": marker vertex id outside [0, V)");
+    if (F == 0) return MOSHII_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (sizeof(T) == 4 && !m->l32_valid) { int rc = moshii_lbs32_prepare(m); if (rc) return rc; }
+    const bool dev = (flags & MOSHII_BUFFERS_DEVICE) != 0;
+    const size_t frame_bytes = (size_t)m->V * 3 * sizeof(T);
+    // frames per batch: 256 MB of meshes (SMPL-H f32: 2 816 frames), whole 128-frame tiles of the f32 export where it reaches one
+    long long batch = std::max<long long>(1, (long long)((size_t)256 << 20) / (long long)frame_bytes);
+    if (batch >= 128) batch = batch / 128 * 128;
+    if (const char* es = getenv("MOSHII_VM_BATCH")) batch = std::max(1, atoi(es));   // (tests: batch boundaries with few frames)
+    batch = std::min<long long>(std::min<long long>(batch, F), 0x7fffffffLL / M);
+    if (sizeof(T) == 8) batch = std::min<long long>(batch, 65535);   // (the f64 export puts the frames on grid.y)
+    const size_t off_vids = ((size_t)batch * frame_bytes + 15) & ~(size_t)15, off_dist = (off_vids + (size_t)M * sizeof(int) + 15) & ~(size_t)15;
+    int rc = m->vmscratch.reserve(off_dist + (size_t)M * sizeof(double));   // (waits for the call before this one)
+    if (rc) return rc;
+    T* d_mesh = reinterpret_cast<T*>(m->vmscratch.ptr);
+    int* d_vids = reinterpret_cast<int*>(m->vmscratch.ptr + off_vids);
+    double* d_dist = reinterpret_cast<double*>(m->vmscratch.ptr + off_dist);
+    std::vector<double> dist64(dist, dist + M);
+    HIP_TRY(hipMemcpy(d_vids, vids, (size_t)M * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_dist, dist64.data(), (size_t)M * sizeof(double), hipMemcpyHostToDevice));
+    const T *d_pose = pose, *d_trans = trans, *d_shape = shape;
+    T *d_out = markers, *d_nrm = mnormals;
+    T *t_pose = nullptr, *t_trans = nullptr, *t_shape = nullptr, *t_out = nullptr, *t_nrm = nullptr;
+    const size_t nout = (size_t)F * M * 3;
+    DevTemps temps;
+    if (!dev) {
+        rc = dev_upload(pose, (size_t)F * m->NP, &t_pose); temps.keep(t_pose);
+        if (rc) return rc;
+        rc = dev_upload(trans, (size_t)F * 3, &t_trans); temps.keep(t_trans);
+        if (rc) return rc;
+        if (shape) { rc = dev_upload(shape, (size_t)F * m->nshape, &t_shape); temps.keep(t_shape); if (rc) return rc; }
+        HIP_TRY(hipMalloc((void**)&t_out, nout * sizeof(T)));
+        temps.keep(t_out);
+        if (mnormals) { HIP_TRY(hipMalloc((void**)&t_nrm, nout * sizeof(T))); temps.keep(t_nrm); }
+        d_pose = t_pose; d_trans = t_trans; d_out = t_out; d_nrm = t_nrm;
+        if (shape) d_shape = t_shape;
+    }
+    m->vmscratch.used = true; m->vmscratch.last_stream = stream;
+    for (long long f0 = 0; f0 < F; f0 += batch) {
+        const int nf = (int)std::min<long long>(batch, F - f0);
+        HIP_TRY(export_batch(m, nf, d_pose + (size_t)f0 * m->NP, d_trans + (size_t)f0 * 3,
+                             d_shape ? d_shape + (size_t)f0 * m->nshape : (const T*)nullptr, d_mesh, stream));
+        HIP_TRY(moshii_launch_marker_normals(stream, m->V, nf, M, sizeof(T) == 8, d_mesh, d_vids, d_dist, d_out + (size_t)f0 * M * 3,
+                                             d_nrm ? d_nrm + (size_t)f0 * M * 3 : (T*)nullptr, m->d_vn_rows, m->d_vn_pairs, m->vn_w16));
+    }
+    if (!dev) {
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemcpy(markers, t_out, nout * sizeof(T), hipMemcpyDeviceToHost));
+        if (mnormals) HIP_TRY(hipMemcpy(mnormals, t_nrm, nout * sizeof(T), hipMemcpyDeviceToHost));
+    }
+    return MOSHII_OK;
+}
+
+extern "C" {
+
+int moshii_virtual_markers_f32(moshii_model_t m, int32_t F, const float* pose, const float* trans, const float* shape, int32_t M,
+                               const int32_t* vids, const float* dist, float* markers, float* marker_normals, uint32_t flags, void* stream) {
+    return virtual_markers_impl(m, F, pose, trans, shape, M, vids, dist, markers, marker_normals, flags, stream, "moshii_virtual_markers_f32");
+}
+int moshii_virtual_markers_f64(moshii_model_t m, int32_t F, const double* pose, const double* trans, const double* shape, int32_t M,
+                               const int32_t* vids, const double* dist, double* markers, double* marker_normals, uint32_t flags, void* stream) {
+    return virtual_markers_impl(m, F, pose, trans, shape, M, vids, dist, markers, marker_normals, flags, stream, "moshii_virtual_markers_f64");
 }
 
 int moshii_prior_create(int32_t G, int32_t npose, const double* means, const double* chols, const double* weights,
@@ -1639,5 +1830,11 @@ const double* moshii_internal_shape_block(moshii_model_t m, int* NB, int* start,
     return m->d_shapedirs;
 }
 void* moshii_internal_l32(moshii_model_t m) { return &m->l32; }
+// device buffers for callers without an allocator of their own (moshpp_amd/capi.py: DeviceBuffer)
+void* moshii_internal_dev_alloc(size_t bytes) { void* p = nullptr; return hipMalloc((void**)&p, bytes ? bytes : 1) == hipSuccess ? p : nullptr; }
+void moshii_internal_dev_free(void* p) { if (p) hipFree(p); }
+int moshii_internal_dev_copy(void* dst, const void* src, size_t bytes, int to_device) {
+    return hipMemcpy(dst, src, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+}
 void moshii_internal_l32_set_valid(moshii_model_t m, int v) { m->l32_valid = v != 0; }
 }

@@ -325,22 +325,17 @@ def _stageii_vertices_plan(pkl, frame_ids):
     return sm, mp, kind, start, count, ids
 
 
-def stageii_vertices(stageii_data_or_fname, surface_model=None, frame_ids=None, dtype=np.float32):
-    """verts[T, V, 3]: the meshes a Stage-II result (pickle file name or dict) describes, frame by frame -- pose, translation,
-    Stage-I betas AND, where the solve freed them, the per-frame expression (optimize_face, SMPL-X) or DMPL coefficients
-    (optimize_dynamics, SMPL / SMPL-H): rest positions and joints move with them exactly as they did in the solve, so the mesh
-    carries the solve's simulated markers.  Every other result (body / finger solves, MANO, the animal models) is a plain export.
-
-    surface_model: a models.SurfaceModel; default: the model file named by the stored cfg.  With optimize_dynamics the DMPL
-    directions of cfg.surface_model.dmpl_fname replace shapedirs[:, :, num_betas : num_betas + num_dmpls] as in the solve; a cfg
-    without dmpl_fname means the given surface_model already holds them there.  frame_ids: rows of the result (default: all).
-    dtype float32: the batched export kernels (|error| <= 2e-5 m); float64: the reference-precision kernel."""
+def _stageii_load(stageii_data_or_fname):
     if isinstance(stageii_data_or_fname, dict):
-        pkl = stageii_data_or_fname
-    else:
-        with open(stageii_data_or_fname, 'rb') as fh:
-            pkl = pickle.load(fh)
-    sm, mp, kind, start, count, ids = _stageii_vertices_plan(pkl, frame_ids)
+        return stageii_data_or_fname
+    with open(stageii_data_or_fname, 'rb') as fh:
+        return pickle.load(fh)
+
+
+def _stageii_export_inputs(pkl, plan, surface_model):
+    """(surface_model, shapedirs, betas, fullpose[ids], trans[ids], coefficients | None) of a planned export: what the model handle
+    of stageii_vertices / stageii_virtual_markers is created from -- no device touched yet."""
+    sm, mp, kind, start, count, ids = plan
     from .models import load_surface_model
     if surface_model is None:
         surface_model = load_surface_model(surface_model_fname=sm['fname'], surface_model_type=sm['type'],
@@ -369,7 +364,12 @@ def stageii_vertices(stageii_data_or_fname, surface_model=None, frame_ids=None, 
     coef = None
     if kind is not None:   # stored: the frozen betas of those columns + the solved offsets
         coef = np.asarray(pkl['expression' if kind == 'expr' else 'dmpls'], dtype=np.float64)[ids, :count] - b[start:start + count]
+    return surface_model, shapedirs, b, fullpose[ids], np.asarray(pkl['trans'], dtype=np.float64)[ids], coef
+
+
+def _stageii_device(surface_model, shapedirs, b, kind, start, count):
     from . import capi
+    K = surface_model.K
     # the pickle holds the FULL pose: every joint's rotation vector is a pose variable of this handle (no hand-PCA map)
     dev = capi.Model(surface_model.v_template, shapedirs, surface_model.posedirs, surface_model.weights, surface_model.J_regressor,
                      surface_model.parents, 3 * K, 0)
@@ -377,6 +377,126 @@ def stageii_vertices(stageii_data_or_fname, surface_model=None, frame_ids=None, 
         dev.set_betas(b)
         if kind is not None:
             dev.set_free_shape(start, count)
-        return dev.lbs_forward(fullpose[ids], np.asarray(pkl['trans'], dtype=np.float64)[ids], dtype=dtype, shape=coef)
+    except Exception:
+        dev.close()
+        raise
+    return dev
+
+
+def stageii_vertices(stageii_data_or_fname, surface_model=None, frame_ids=None, dtype=np.float32, return_normals=False):
+    """verts[T, V, 3]: the meshes a Stage-II result (pickle file name or dict) describes, frame by frame -- pose, translation,
+    Stage-I betas AND, where the solve freed them, the per-frame expression (optimize_face, SMPL-X) or DMPL coefficients
+    (optimize_dynamics, SMPL / SMPL-H): rest positions and joints move with them exactly as they did in the solve, so the mesh
+    carries the solve's simulated markers.  Every other result (body / finger solves, MANO, the animal models) is a plain export.
+
+    surface_model: a models.SurfaceModel; default: the model file named by the stored cfg.  With optimize_dynamics the DMPL
+    directions of cfg.surface_model.dmpl_fname replace shapedirs[:, :, num_betas : num_betas + num_dmpls] as in the solve; a cfg
+    without dmpl_fname means the given surface_model already holds them there.  frame_ids: rows of the result (default: all).
+    dtype float32: the batched export kernels (|error| <= 2e-5 m); float64: the reference-precision kernel.
+    return_normals: (verts, normals) -- the area-weighted unit vertex normals [T, V, 3] of the same frames and dtype, computed on
+    the device from the exported buffer (the model needs its triangles `f`)."""
+    pkl = _stageii_load(stageii_data_or_fname)
+    plan = _stageii_vertices_plan(pkl, frame_ids)
+    if return_normals and surface_model is not None and getattr(surface_model, 'f', None) is None:
+        raise ValueError('stageii_vertices: return_normals needs a surface model with faces (f)')
+    sm, mp, kind, start, count, ids = plan
+    surface_model, shapedirs, b, fullpose, trans, coef = _stageii_export_inputs(pkl, plan, surface_model)
+    if return_normals and getattr(surface_model, 'f', None) is None:
+        raise ValueError('stageii_vertices: return_normals needs a surface model with faces (f)')
+    dev = _stageii_device(surface_model, shapedirs, b, kind, start, count)
+    try:
+        if not return_normals:
+            return dev.lbs_forward(fullpose, trans, dtype=dtype, shape=coef)
+        dev.set_faces(surface_model.f)
+        return dev.lbs_forward_with_normals(fullpose, trans, dtype=dtype, shape=coef)
     finally:
         dev.close()
+
+
+DEFAULT_M2B_DISTANCE = 0.0095     # prepare_mosh_markers_latent's default distance from skin (chmosh.py:59)
+
+
+def _virtual_marker_layout(marker_layout):
+    """(labels, vids[M], m2b[M], surface_model_type | None) of a layout: a json file name, the dict marker_layout_load returns, or a
+    plain label -> vertex id dict (0.0095 m for every marker).  Distances as prepare_mosh_markers_latent takes them
+    (chmosh.py:57-64): 0.0095 by default, m2b_distance[type] under each marker_type_mask."""
+    if isinstance(marker_layout, (str, os.PathLike)):
+        from .marker_layout import marker_layout_load
+        marker_layout = marker_layout_load(str(marker_layout))
+    if not isinstance(marker_layout, dict) or not len(marker_layout):
+        raise ValueError('stageii_virtual_markers: marker_layout must be a layout file name, a loaded layout or a label -> vertex id dict')
+    if 'marker_vids' in marker_layout:
+        meta = marker_layout
+        labels = list(meta['marker_vids'].keys())
+        raw = list(meta['marker_vids'].values())
+        model_type = meta.get('surface_model_type')
+    else:
+        meta = None
+        labels = list(marker_layout.keys())
+        raw = list(marker_layout.values())
+        model_type = None
+    if any(isinstance(v, (list, tuple, np.ndarray)) for v in raw):
+        raise ValueError('stageii_virtual_markers: a superset layout (several vertex ids per label) places no single marker; '
+                         'pick one vertex per label first')
+    vids = np.asarray(raw)
+    if not np.issubdtype(vids.dtype, np.integer) or (len(vids) and vids.min() < 0):
+        raise ValueError('stageii_virtual_markers: vertex ids must be non-negative integers')
+    m2b = np.full(len(labels), DEFAULT_M2B_DISTANCE)
+    if meta is not None:
+        for mask_type, mask in meta.get('marker_type_mask', {}).items():
+            m2b[np.asarray(mask, dtype=bool)] = float(meta['m2b_distance'][mask_type])
+    return labels, vids.astype(np.int32), m2b, model_type
+
+
+def _stageii_virtual_markers_plan(pkl, marker_layout, surface_model, frame_ids, out_fname):
+    """Every refusal of stageii_virtual_markers that needs no model file and no device."""
+    plan = _stageii_vertices_plan(pkl, frame_ids)
+    labels, vids, m2b, layout_type = _virtual_marker_layout(marker_layout)
+    sm = plan[0]
+    if layout_type is not None and layout_type != sm['type']:
+        raise ValueError(f"stageii_virtual_markers: the layout is for {layout_type}, the Stage-II result for {sm['type']}")
+    if out_fname is not None and not str(out_fname).endswith(('.c3d', '.npz')):
+        raise ValueError(f'stageii_virtual_markers: out_fname must end in .c3d or .npz: {out_fname}')
+    if out_fname is not None and 'mocap_frame_rate' not in pkl['stageii_debug_details']:
+        raise KeyError("stageii_virtual_markers: the Stage-II data stores no frame rate (stageii_debug_details['mocap_frame_rate']) "
+                       "to write the file with")
+    if surface_model is not None:
+        if getattr(surface_model, 'f', None) is None:
+            raise ValueError('stageii_virtual_markers: the surface model has no faces (f)')
+        if len(vids) and vids.max() >= surface_model.V:
+            raise ValueError(f'stageii_virtual_markers: vertex ids beyond the {surface_model.V} vertices of the model')
+    return plan, labels, vids, m2b
+
+
+def stageii_virtual_markers(stageii_data_or_fname, marker_layout, surface_model=None, frame_ids=None, dtype=np.float32, out_fname=None):
+    """dict(markers[T, M, 3], labels, vids, m2b): the markers a layout would carry on every frame of a Stage-II result --
+    vertex + vertex normal x distance-from-skin, the reference's rule for ONE canonical body (prepare_mosh_markers_latent,
+    chmosh.py:57-67; marker_layout_to_c3d, marker_layout/edit_tools.py) on each solved frame's mesh: synthetic mocap, re-targeting a
+    capture to another layout, filling markers the capture never had.  The meshes stay on the device.
+
+    marker_layout: a layout json file name, the dict marker_layout_load returns, or a plain label -> vertex id dict (0.0095 m for
+    every marker).  surface_model / frame_ids / dtype / per-frame expression and DMPL coefficients: as in stageii_vertices.
+    out_fname: '.c3d' (write_mocap_c3d) or '.npz' (markers, labels, frame_rate as MocapSession reads them), at the frame rate the
+    Stage-II result stores (a result without one is a KeyError, raised before any work)."""
+    pkl = _stageii_load(stageii_data_or_fname)
+    plan, labels, vids, m2b = _stageii_virtual_markers_plan(pkl, marker_layout, surface_model, frame_ids, out_fname)
+    sm, mp, kind, start, count, ids = plan
+    surface_model, shapedirs, b, fullpose, trans, coef = _stageii_export_inputs(pkl, plan, surface_model)
+    if getattr(surface_model, 'f', None) is None:
+        raise ValueError('stageii_virtual_markers: the surface model has no faces (f)')
+    if len(vids) and vids.max() >= surface_model.V:
+        raise ValueError(f'stageii_virtual_markers: vertex ids beyond the {surface_model.V} vertices of the model')
+    dev = _stageii_device(surface_model, shapedirs, b, kind, start, count)
+    try:
+        dev.set_faces(surface_model.f)
+        markers = dev.virtual_markers(fullpose, trans, vids, m2b, dtype=dtype, shape=coef)
+    finally:
+        dev.close()
+    if out_fname is not None:
+        rate = float(pkl['stageii_debug_details']['mocap_frame_rate'])
+        if str(out_fname).endswith('.c3d'):
+            from .mocap_interface import write_mocap_c3d
+            write_mocap_c3d(markers, labels, _makepath(str(out_fname)), frame_rate=rate)
+        else:
+            np.savez(_makepath(str(out_fname)), markers=markers, labels=labels, frame_rate=rate)
+    return dict(markers=markers, labels=labels, vids=vids, m2b=m2b)

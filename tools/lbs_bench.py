@@ -1,10 +1,96 @@
 """Time the full-mesh LBS export kernels alone (for rocprofv3): python tools/lbs_bench.py [F] [reps] [model] [--shape E] [--repeats N]
 --shape E: the export with per-frame coefficients of a free shape block of E columns (moshii_lbs_forward_shape_f32) -- the body gets E
 extra shapedirs columns (a unit coefficient moves a vertex by up to 1 cm), the coefficients are N(0, 1); same poses otherwise.
---repeats N: N timed rounds of `reps` calls each, one line per round (run-to-run spread)."""
+--repeats N: N timed rounds of `reps` calls each, one line per round (run-to-run spread).
+--normals [F] [reps] [--model NAME]: vertex normals and virtual markers of exported meshes on the triangulated synthetic body of the
+family (synth.synth_mesh_model, seed 1000; default smplh, 4000 frames): the export alone, the normals alone through the LDS kernel
+and through the gather kernel, export + normals, and the virtual-marker call for 53 markers -- HIP events on device buffers, us and the
+fraction of 8 TB/s under F V 24 B + the face table."""
 import ctypes as C, sys, time
 import numpy as np
 sys.path.insert(0, '.')
+
+
+def normals_bench(argv):
+    import os
+    import torch
+    from moshpp_amd import synth, workload
+    mt = 'smplh'
+    if '--model' in argv:
+        i = argv.index('--model')
+        mt = argv[i + 1]
+        del argv[i:i + 2]
+    F = int(argv[0]) if len(argv) > 0 else 4000
+    reps = int(argv[1]) if len(argv) > 1 else 10
+    M = {'smplh': 53, 'smpl': 41, 'smplx': 89, 'mano': 33}[mt]
+    dd = synth.synth_mesh_model(mt, seed=1000)
+    job = workload.make_job(mt, 8, M, seed=1000, optimize_fingers=(mt == 'mano'), dd=dd)
+    solver = workload.make_solver(job)
+    model, sm = solver.dev, job['sm']
+    faces = np.asarray(dd['f'], dtype=np.int32)
+    model.set_faces(faces)
+    V = sm.V
+    good = (faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 0] != faces[:, 2])
+    table = (V + 1) * 4 + 3 * int(good.sum()) * (4 if V <= 65535 else 8)
+    val = np.bincount(faces.ravel(), minlength=V)
+    dev = torch.device('cuda', 0)
+    rng = np.random.default_rng(0)
+    pose = torch.from_numpy(rng.normal(0, 0.3, (F, sm.NP)).astype(np.float32)).to(dev)
+    trans = torch.from_numpy(rng.normal(0, 1, (F, 3)).astype(np.float32)).to(dev)
+    verts = torch.empty((F, V, 3), dtype=torch.float32, device=dev)
+    normals = torch.empty((F, V, 3), dtype=torch.float32, device=dev)
+    vids = rng.choice(V, 53, replace=False).astype(np.int32)
+    dist = np.full(53, 0.0095)
+    mk = torch.empty((F, 53, 3), dtype=torch.float32, device=dev)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    export = lambda: model.lbs_forward_device(F, pose.data_ptr(), trans.data_ptr(), verts.data_ptr(), stream)
+    nrm = lambda: model.vertex_normals_device(F, verts.data_ptr(), normals.data_ptr(), stream)
+    both = lambda: (export(), nrm())
+    vm = lambda: model.virtual_markers_device(F, pose.data_ptr(), trans.data_ptr(), vids, dist, mk.data_ptr(), None, stream)
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(3):              # three rounds: the spread
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) * 1e-3 / reps)
+        return min(ts), max(ts)
+
+    print(f'{mt} mesh body: V = {V}, {len(faces)} faces, valence {val.min()} .. {val.max()}, face table {table / 1e3:.1f} KB, F = {F}, '
+          f'{reps} calls a round, 3 rounds (fastest .. slowest round); library {os.path.basename(capi.LIB_PATH)} {capi.load().moshii_source_hash().decode()}')
+    nb = F * V * 24 + table
+    legs = [('export alone', export, F * V * 12, 'F V 12 B'), ('normals, LDS kernel', nrm, nb, 'F V 24 B + table')]
+    for name, fn, nbytes, what in legs:
+        lo, hi = timed(fn)
+        print(f'  {name:34s} {lo * 1e6:8.1f} .. {hi * 1e6:8.1f} us   {nbytes / lo / 8e12 * 100:5.1f} % of 8 TB/s under {what}')
+    kname, klds, kthreads = capi.last_launch_info()
+    assert kname == 'k_vn_lds', kname
+    print(f'  ({kname}: {klds} B of LDS a workgroup, {kthreads} threads)')
+    os.environ['MOSHII_VN_KERNEL'] = 'gather'
+    lo, hi = timed(nrm)
+    del os.environ['MOSHII_VN_KERNEL']
+    assert capi.last_launch_info()[0] == 'k_vn_gather<float>', capi.last_launch_info()
+    print(f'  {"normals, gather kernel":34s} {lo * 1e6:8.1f} .. {hi * 1e6:8.1f} us   {nb / lo / 8e12 * 100:5.1f} % of 8 TB/s under F V 24 B + table')
+    lo, hi = timed(both)
+    print(f'  {"export + normals":34s} {lo * 1e6:8.1f} .. {hi * 1e6:8.1f} us   {(F * V * 36 + table) / lo / 8e12 * 100:5.1f} % of 8 TB/s under F V 36 B + table')
+    lo, hi = timed(vm)
+    print(f'  {"virtual markers, 53 markers":34s} {lo * 1e6:8.1f} .. {hi * 1e6:8.1f} us   (meshes in the handle\'s scratch; {F * 53 * 12 / 1e6:.1f} MB reach the caller)')
+    ref = model.vertex_normals(verts[:2].cpu().numpy())
+    print(f'  check: device-buffer normals vs the host-buffer call on 2 frames: max |diff| {np.abs(normals[:2].cpu().numpy() - ref).max():.1e}')
+
+
+if '--normals' in sys.argv:
+    from moshpp_amd import capi
+    sys.argv.remove('--normals')
+    normals_bench(sys.argv[1:])
+    sys.exit(0)
 E_SHAPE, REPEATS = 0, 1
 for flag in ('--shape', '--repeats'):
     if flag in sys.argv:

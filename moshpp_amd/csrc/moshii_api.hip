@@ -1016,7 +1016,7 @@ int prepare_launch(moshii_model_t m, moshii_prior_t prior, const moshii_solve_op
     const int xt = (nshape > 0 || o->n_face > 0) ? 1 : 0;
     const int nmax = 3 + std::max(o->n_step1, o->n_step2 + nshape);
     int nblk = pick_nblk(nmax, xt != 0);
-    if (nblk < 0) return fail(MOSHII_ERR_UNSUPPORTED, xt ? "more than 207 unknowns per step" : "more than 125 free pose variables per step");
+    if (nblk < 0) return fail(MOSHII_ERR_UNSUPPORTED, xt ? "more than 207 unknowns per step" : "more than 124 free pose variables per step");
     if (const char* e = getenv("MOSHII_FORCE_NBLK")) nblk = std::max(nblk, atoi(e));
     auto count_kf = [&](const int32_t* ids, int n) {   // needed joints (superset over both steps)
         std::vector<char> need(m->K, 0);

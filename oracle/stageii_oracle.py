@@ -739,7 +739,7 @@ class StageIIObjective:
 
 def stageii_chain(m, prior, closest, coef, obs, vis, model_type, weights=None, optimize_fingers=False,
                   optimize_toes=False, maxiter=100, reference_cost=False, init=None, num_train_markers=46,
-                  collect_stats=False, optimize_face=False, free_shape=None):
+                  collect_stats=False, optimize_face=False, free_shape=None, id_sets=None):
     """The Stage-II frame loop, chmosh.py:584-724, on array inputs:
     obs[F,M,3] (metres), vis[F,M] bool (marker of latent label i observed in frame t).
     `init` = None -> first-frame schedule (rigid init + 3 annealed rounds, chmosh.py:629-655);
@@ -749,11 +749,14 @@ def stageii_chain(m, prior, closest, coef, obs, vis, model_type, weights=None, o
     'dmpl' -> regulariser stageii_wt_dmpl plus `extrap_dmpl` (:693-699).  As written in the reference, `dmpl_prev` is
     refreshed (:658-659) BEFORE the term is built, so (dmpl - (dmpl.r + (dmpl.r - dmpl_prev))) * 6 evaluates to
     (dmpl - value at frame start) * 6, from the second solved frame on.
+    `id_sets` = (body, finger, step1, step2) replaces what pose_id_sets returns (any sorted free sets; the tests' size-class edges).
     Returns dict(fullpose[F',P], trans[F',3], markers_sim[list], frame_ids[F'], errs{term: array}, pose[F',NP],
     shape[F',E])."""
     W = stageii_weights_default() if weights is None else dict(weights)
     NP = m['NP']
     root, body, finger, step1, step2 = pose_id_sets(model_type, NP, optimize_fingers, optimize_toes, optimize_face)
+    if id_sets is not None:
+        body, finger, step1, step2 = (list(a) for a in id_sets)
     face = face_pose_ids(model_type, optimize_face)
     objf = StageIIObjective(m, closest, coef, prior, body, reference_cost=reference_cost)
     assert free_shape in (None, 'expr', 'dmpl')

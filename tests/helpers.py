@@ -45,8 +45,9 @@ def oracle_case(model_type='smplh', F=12, M=53, seed=0, **kw):
 
 
 def device_case(case, optimize_fingers=False, optimize_toes=False, maxiter=100, weights=None, optimize_face=False,
-                shape_kind=None):
-    """libmoshii handles + options for an oracle_case / shape_case (same arrays, same ids)."""
+                shape_kind=None, id_sets=None):
+    """libmoshii handles + options for an oracle_case / shape_case (same arrays, same ids).  id_sets = (body, finger, step1, step2):
+    these lists instead of pose_id_sets' (as stageii_chain(..., id_sets=...) takes them)."""
     from moshpp_amd import capi
     mdl = case['model']
     m = case['m']
@@ -61,6 +62,8 @@ def device_case(case, optimize_fingers=False, optimize_toes=False, maxiter=100, 
         pr = capi.Prior(case['prior']['means'], case['prior']['chols'], case['prior']['weights'])
     root, body, finger, st1, st2 = so.pose_id_sets(case['model_type'], m['NP'], optimize_fingers, optimize_toes,
                                                    optimize_face=optimize_face)
+    if id_sets is not None:
+        body, finger, st1, st2 = (list(a) for a in id_sets)
     W = so.stageii_weights_default() if weights is None else weights
     opts = capi.make_opts(W, st1, st2, body, finger if optimize_fingers else [], maxiter=maxiter,
                           face_ids=so.face_pose_ids(case['model_type'], optimize_face),

@@ -3139,8 +3139,8 @@ __global__ __launch_bounds__(MOSHII_TPB, MINW) void k_chain_solve(const ChainDev
                         if (tid == 3) so[2 * NP + 3] = flag;
                         if (tid == 4) so[2 * NP + 4] = 0.0;
                     };
-                    spoil(chp->entry_state, -1.0);      // (both slots exist for every chain of a chunked solve's first launch)
-                    spoil(chp->final_state, -2.0);
+                    spoil(chp->entry_state, MOSHII_MARK_ENTRY_SPOILED);      // (both slots exist for every chain of a chunked solve's first launch)
+                    spoil(chp->final_state, MOSHII_MARK_FINAL_SPOILED);
                     if (tid == 0 && chp->tail_mark != nullptr) *chp->tail_mark = 0x7fffffff;   // (no sweep re-joins inside this chunk: its rows are a mix)
                     tail_cut = true;
                     break;
@@ -3199,7 +3199,7 @@ __global__ __launch_bounds__(MOSHII_TPB, MINW) void k_chain_solve(const ChainDev
                         __syncthreads();
                         if (cx.scal[S_ABORT] != 0.0) {
                             if (tid == 0) {
-                                chp->run_entry[(size_t)bi_next * S + 2 * NP + 3] = -1.0;
+                                chp->run_entry[(size_t)bi_next * S + 2 * NP + 3] = MOSHII_MARK_ENTRY_SPOILED;
                                 int* mark = chp->abort_at + chp->chunk0 + bi_next;
                                 if (*mark < chp->bnd_off + t) *mark = chp->bnd_off + t;
                                 if (chp->frames_done) *chp->frames_done = -t - 1;
@@ -3261,10 +3261,10 @@ __global__ __launch_bounds__(MOSHII_TPB, MINW) void k_chain_solve(const ChainDev
                     double dv = 0.0, nn = 0.0;
                     for (int i = tid; i < NP; i += MOSHII_TPB) { dv = fmax(dv, fmax(fabs(cx.pose[i] - en[i]), fabs(cx.pose_prev[i] - en[NP + i]))); nn += en[i] + en[NP + i]; }
                     if (tid < 3) dv = fmax(dv, fabs(cx.trans[tid] - en[2 * NP + tid]));
-                    if (tid == 3 && (has_prev ? 1.0 : 0.0) != en[2 * NP + 3]) dv = 1e300;
-                    if (tid == 4 && (first ? 1.0 : 0.0) != en[2 * NP + 4]) dv = 1e300;
+                    if (tid == 3 && (has_prev ? 1.0 : 0.0) != en[2 * NP + 3]) dv = MOSHII_HANDOFF_MISMATCH;
+                    if (tid == 4 && (first ? 1.0 : 0.0) != en[2 * NP + 4]) dv = MOSHII_HANDOFF_MISMATCH;
                     if constexpr (XT) for (int e = tid; e < op.nshape; e += MOSHII_TPB) dv = fmax(dv, fabs(cx.pose[NP + e] - en[2 * NP + 5 + e]));
-                    if (!(nn == nn)) dv = 1e300;
+                    if (!(nn == nn)) dv = MOSHII_HANDOFF_MISMATCH;
                     return block_max(dv, cx.red);
                 };
                 auto wait_flag = [&](int* fl, int patience) {   // thread 0 waits (bounded) for *fl == 1; every thread gets the outcome
@@ -3402,7 +3402,7 @@ __global__ __launch_bounds__(MOSHII_TPB, MINW) void k_chain_solve(const ChainDev
             if (cx.scal[S_ABORT] != 0.0) {
                 if (tid == 0) {
                     const int S = 2 * NP + 5 + (XT ? op.nshape : 0);
-                    chp->run_entry[(size_t)bi_next * S + 2 * NP + 3] = -1.0;
+                    chp->run_entry[(size_t)bi_next * S + 2 * NP + 3] = MOSHII_MARK_ENTRY_SPOILED;
                     // ... and whoever re-solves this chunk starts by reproducing THIS chain's rows: it must not take that for
                     // having re-joined before it is past frame t
                     int* mark = chp->abort_at + chp->chunk0 + bi_next;
@@ -3551,7 +3551,7 @@ __global__ __launch_bounds__(MOSHII_TPB, MINW) void k_chain_solve(const ChainDev
         // check looks -- spoil that chunk's entry state so that the next verification re-solves it (as a stopped plain chain does)
         if (cx.scal[S_COOP_FAIL] != 0.0 && lead && tid == 0 && chp->run_entry != nullptr) {
             const int S = 2 * NP + 5;
-            chp->run_entry[(size_t)bi_next * S + 2 * NP + 3] = -1.0;
+            chp->run_entry[(size_t)bi_next * S + 2 * NP + 3] = MOSHII_MARK_ENTRY_SPOILED;
             if (chp->abort_at != nullptr) chp->abort_at[chp->chunk0 + bi_next] = 0x7fffffff;   // (nothing behind the break counts as re-joined)
         }
         // (a cooperative repair chain: EVERY rank's rows -- the simulated markers are written rank by rank -- are out before rank 0 says so)
@@ -3647,13 +3647,13 @@ __global__ __launch_bounds__(MOSHII_TPB) void k_markers(const AttachDev* __restr
 
 // coop_g >= 1: cooperative chains, coop_g workgroups per chain (every ChainDev::coop of the launch is filled in for that group size);
 // the grid is 8 coop_g ceil(n_chains / 8) blocks, of which those beyond the last chain return at once (block -> (chain, rank): k_chain_solve).
-extern "C" hipError_t moshii_launch_chain_solve(int nblk, int two_per_cu, int xt, int n_chains, size_t lds_bytes, hipStream_t stream,
+extern "C" hipError_t moshii_launch_chain_solve(int nblk, int xt, int n_chains, size_t lds_bytes, hipStream_t stream,
                                                 const ChainDev* chains, const ModelDev* md, const PriorDev* pr,
                                                 const OptsDev* op, const ChainLayout* ly, int coop_g) {
     using namespace moshii;
     void (*kern)(const ChainDev*, ModelDev, PriorDev, OptsDev, ChainLayout, int) = nullptr;
 #ifdef MOSHII_DEV_ONLY_NBLK4
-    if (xt || nblk != 4 || two_per_cu) return hipErrorInvalidValue;
+    if (xt || nblk != 4) return hipErrorInvalidValue;
     if (coop_g >= 1) kern = k_chain_solve<4, 1, false, true>; else kern = k_chain_solve<4, 1, false, false>;
 #else
     if (coop_g >= 1 && xt) {
@@ -3680,15 +3680,15 @@ extern "C" hipError_t moshii_launch_chain_solve(int nblk, int two_per_cu, int xt
             case 13: kern = k_chain_solve<13, 1, true>; break;
             default: return hipErrorInvalidValue;
         }
-    } else switch (nblk * 2 + (two_per_cu ? 1 : 0)) {
+    } else switch (nblk) {
         // (the 256-register instantiations <N, 2> -- two workgroups per CU, 1.9x slower per chain for +6 % aggregate throughput -- were
         //  removed in round 3; a build without them times 262-264 us per frame against 266-267 with them on the same box.  The "14 %
         //  slower without them" of an earlier commit was a slow box: profiles/r03_bench_line_slow_box.json)
-        case 4: kern = k_chain_solve<2, 1, false>; break;
-        case 8: kern = k_chain_solve<4, 1, false>; break;
-        case 10: kern = k_chain_solve<5, 1, false>; break;
-        case 14: kern = k_chain_solve<7, 1, false>; break;
-        case 16: kern = k_chain_solve<8, 1, false>; break;
+        case 2: kern = k_chain_solve<2, 1, false>; break;
+        case 4: kern = k_chain_solve<4, 1, false>; break;
+        case 5: kern = k_chain_solve<5, 1, false>; break;
+        case 7: kern = k_chain_solve<7, 1, false>; break;
+        case 8: kern = k_chain_solve<8, 1, false>; break;
         default: return hipErrorInvalidValue;
     }
 #endif

@@ -1,6 +1,7 @@
 // libmoshii C ABI (include/moshii.h): handles, setup kernels, host-side staging and launch logic.
 #include "../../include/moshii.h"
 #include "moshii_dev.h"
+#include "solve_plan.h"
 #include "stagei_views.h"
 
 #include <algorithm>
@@ -12,7 +13,7 @@
 #include <string>
 #include <vector>
 
-extern "C" hipError_t moshii_launch_chain_solve(int nblk, int two_per_cu, int xt, int n_chains, size_t lds_bytes, hipStream_t stream,
+extern "C" hipError_t moshii_launch_chain_solve(int nblk, int xt, int n_chains, size_t lds_bytes, hipStream_t stream,
                                                 const ChainDev* chains, const ModelDev* md, const PriorDev* pr,
                                                 const OptsDev* op, const ChainLayout* ly, int coop_g);
 extern "C" hipError_t moshii_launch_markers(int F, size_t lds_bytes, hipStream_t stream, const AttachDev* att,
@@ -62,6 +63,11 @@ struct Scratch {   // growable device buffer reused across calls (small control 
         if (hipMalloc((void**)&ptr, want) != hipSuccess) return fail(MOSHII_ERR_HIP, "scratch hipMalloc failed");
         cap = want;
         return MOSHII_OK;
+    }
+    int reserve(size_t bytes, hipStream_t stream) {   // ... and the buffer is in use on `stream` until the next reserve
+        const int rc = reserve(bytes);
+        if (rc == MOSHII_OK) { used = true; last_stream = stream; }
+        return rc;
     }
     ~Scratch() { if (ptr) hipFree(ptr); }
 };
@@ -927,16 +933,20 @@ int moshii_attach_markers(moshii_attach_t a, int32_t F, const double* pose, cons
 }  // extern "C" (reopened below)
 
 // ---- shared launch preparation for moshii_chain_solve / moshii_sequence_solve -----------------------
+// (the arithmetic of the plan -- chunk table, group choice, exchange layout, repair scheduling -- is solve_plan.h)
 namespace {
+using solve_plan::Chunk;
+using solve_plan::CoopLayout;
+using solve_plan::coop_split;
+static_assert(solve_plan::kThreads == MOSHII_TPB && solve_plan::kMaxGroup == MOSHII_COOP_MAXG, "solve_plan.h restates them");
 
 struct LaunchCfg {
     int nblk = 0;
-    int two_per_cu = 0;
     int xt = 0;                 // extended kernel variant (jaw term / free shape block)
     int coop_g = 0;             // > 0: cooperative chains, this many workgroups per chain
     int coop_prior_rank = 0;
-    int coop_slot_doubles = 0;
     double coop_prior_frac = 0.4;
+    CoopLayout coop;            // cooperative chains: one chain's slice of the exchange buffer
     ChainLayout ly;
     size_t lds_bytes = 0;
     OptsDev od;
@@ -944,11 +954,12 @@ struct LaunchCfg {
     ModelDev md;
 };
 
-// Validates the options, picks the J^T J register tiling and the LDS layout (marker-tile size Tm as large as the
-// per-workgroup LDS budget allows) and uploads the id lists.  `extra_bytes` of the model's control scratch are
-// reserved after the id lists; their device/host offsets come back through ctl_off.
-// The cooperative-chain request of a call: MOSHII_COOP_GROUP(g) in `flags` (0 = no word: the environment variable `env`, else the library's
-// choice; 1 = plain chains; 2 .. 8 = that many workgroups per chain).  Returns -1 (library's choice), 0 (plain), g, or -2 (out of range).
+int cu_count() {
+    int n_cu = 256;
+    { int dev = 0; hipGetDevice(&dev); hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev); if (n_cu < 1) n_cu = 256; }
+    return n_cu;
+}
+
 // Set once a cooperative group has broken up in this process (a rank did not become resident within the wait limit: the device is
 // shared with another process, or CUs are masked): from then on the library's OWN choice is plain chains -- every further call would
 // pay the wait limit and the repeated solve again.  An explicit MOSHII_COOP_GROUP(g) / MOSHII_COOP=g request is still honoured.
@@ -962,6 +973,8 @@ int coop_skew_env() {
     const char* e = getenv("MOSHII_COOP_SKEW");
     return (e && *e) ? atoi(e) : 0;
 }
+// The cooperative-chain request of a call: MOSHII_COOP_GROUP(g) in `flags` (0 = no word: the environment variable `env`, else the library's
+// choice; 1 = plain chains; 2 .. 8 = that many workgroups per chain).  Returns -1 (library's choice), 0 (plain), g, or -2 (out of range).
 int coop_request(uint32_t flags, const char* env) {
     int g = (int)((flags >> 8) & 0xffu);
     if (g == 0) {
@@ -982,22 +995,10 @@ int coop_request(uint32_t flags, const char* env) {
     return g;
 }
 
-// Cooperative chains: the markers [mlo[r], mlo[r + 1]) of rank r.  The ranks 0 .. G-2 get equal shares, the last rank -- which also
-// evaluates the prior for the group -- `prior_frac` of one (MOSHII_COOP_PRIOR_FRAC; 1 without a prior).
-void coop_split(int M, int G, double prior_frac, int* mlo) {
-    const double w_last = (G > 1) ? prior_frac : 1.0;
-    const double total = (G - 1) + w_last;
-    double acc = 0.0;
-    mlo[0] = 0;
-    for (int r = 0; r < G; ++r) {
-        acc += (r == G - 1) ? w_last : 1.0;
-        mlo[r + 1] = (r == G - 1) ? M : std::min(M, (int)std::lround(M * acc / total));
-        if (mlo[r + 1] < mlo[r]) mlo[r + 1] = mlo[r];
-    }
-}
+// prepare_launch, part 1: validates the options; the sizes that follow from them
+struct SolveDims { int xt, nshape, nmax, nblk, nkfmax, nhj, G, npose; };
 
-int prepare_launch(moshii_model_t m, moshii_prior_t prior, const moshii_solve_opts* o, int Mmax, int Nvmax, int NWmax,
-                   int n_workgroups, hipStream_t stream, size_t extra_bytes, LaunchCfg* cfg, size_t* ctl_off, int coop_g = 0) {
+int check_opts(moshii_model_t m, moshii_prior_t prior, const moshii_solve_opts* o, SolveDims* d) {
     if (!m->betas_set) return fail(MOSHII_ERR_ARG, "moshii_model_set_betas has not been called");
     if (o->n_body > 0 && (!prior || prior->npose != o->n_body)) return fail(MOSHII_ERR_ARG, "prior npose must equal n_body");
     if (o->n_step1 < 0 || o->n_step2 < 0 || o->n_step1 > m->NP || o->n_step2 > m->NP) return fail(MOSHII_ERR_ARG, "bad free-variable lists");
@@ -1029,40 +1030,40 @@ int prepare_launch(moshii_model_t m, moshii_prior_t prior, const moshii_solve_op
     };
     const int kf1 = count_kf(o->step1_ids, o->n_step1), kf2 = count_kf(o->step2_ids, o->n_step2);
     if (kf1 < 0 || kf2 < 0) return fail(MOSHII_ERR_ARG, "free pose id out of range");
-    const int nkfmax = std::max(1, std::max(kf1, kf2));
     if (o->n_finger > 0)
         for (int i = 1; i < o->n_finger; ++i)
             if (o->finger_ids[i] != o->finger_ids[i - 1] + 1) return fail(MOSHII_ERR_UNSUPPORTED, "finger ids must be contiguous");
-    const int G = prior ? prior->G : 0, npose = prior ? prior->npose : 0;
-    // LDS budget per workgroup: a lone chain may take the whole CU (160 KiB); a grid that fills the chip leaves
-    // room for two workgroups per CU so that one chain's dependency stalls are covered by the other's work.
-    int n_cu = 256;
-    { int dev = 0; hipGetDevice(&dev); hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev); if (n_cu < 1) n_cu = 256; }
-    // One workgroup per CU: a 256-register variant (two per CU) spilled and was measured slower per chain by 1.9x for +6 %
-    // aggregate throughput (round 1, tools/gpu_occupancy.py); it was removed in round 3.
-    const int two_per_cu = 0;
-    (void)n_workgroups;
-    int budget = two_per_cu ? 80 * 1024 : 160 * 1024;
-    if (const char* e = getenv("MOSHII_LDS_BUDGET")) budget = atoi(e);
     // hand joints whose d marker / d fullpose must be parked for the PCA contraction (only when hand coefficients are free)
     bool hand_free = false;
     for (int i = 0; i < o->n_step1; ++i) hand_free |= o->step1_ids[i] >= m->body_dof;
     for (int i = 0; i < o->n_step2; ++i) hand_free |= o->step2_ids[i] >= m->body_dof;
-    const int nhj = hand_free ? (m->K - m->body_dof / 3) : 0;
+    d->xt = xt; d->nshape = nshape; d->nmax = nmax; d->nblk = nblk;
+    d->nkfmax = std::max(1, std::max(kf1, kf2));
+    d->nhj = hand_free ? (m->K - m->body_dof / 3) : 0;
+    d->G = prior ? prior->G : 0; d->npose = prior ? prior->npose : 0;
+    return MOSHII_OK;
+}
+
+// prepare_launch, part 2: the J^T J register tiling and the LDS layout -- marker-tile size Tm as large as the per-workgroup LDS
+// budget allows; for cooperative chains one tile of a rank's largest possible share.
+// coop_g: -1 = the library's choice, 0 = plain chains, 2 .. 8 = that many workgroups per chain.  The library chooses a group
+// (solve_plan::own_group_size) when every workgroup of the launch can be resident at once (n_workgroups chains x g <= CUs).
+int choose_layout(moshii_model_t m, const SolveDims& d, int Mmax, int Nvmax, int NWmax, int n_workgroups, int coop_g, LaunchCfg* cfg) {
+    const int xt = d.xt, nmax = d.nmax, npose = d.npose;
+    int nblk = d.nblk;
+    auto layout = [&](int Tm) { return make_layout(m, Mmax, Nvmax, NWmax, npose, d.G, nmax, d.nkfmax, Tm, nblk, d.nhj, d.nshape); };
+    // LDS budget per workgroup: the whole CU (160 KiB).  One workgroup per CU: a 256-register variant (two per CU) spilled and was
+    // measured slower per chain by 1.9x for +6 % aggregate throughput (round 1, tools/gpu_occupancy.py); it was removed in round 3.
+    const int n_cu = cu_count();
+    int budget = 160 * 1024;
+    if (const char* e = getenv("MOSHII_LDS_BUDGET")) budget = atoi(e);
     // Marker-tile size Tm (T0 maps tile vertices to threads 0..127: 3 Tm <= 120).  The Jacobian rows of a tile are built by
     // (tile marker, needed joint) items, 256 at a time, so among the sizes that fit the LDS budget take the one with the
     // fewest item rounds + tiles over a fully visible frame (53 markers x 20 joints: 38 + 15 = 3 + 2 rounds, where two equal
     // tiles of 27 / 26 cost 3 + 3), weighted by what a round and a tile's fixed work cost (about 3 : 4).
-    int Tm = std::min(40, std::max(2, Mmax));
-    ChainLayout ly = make_layout(m, Mmax, Nvmax, NWmax, npose, G, nmax, nkfmax, Tm, nblk, nhj, nshape);
-    // coop_g: -1 = the library's choice, 0 = plain chains, 2 .. 8 = that many workgroups per chain.  The choice: one rank per round of
-    // (marker, joint) Jacobian items (256 threads build 256 of them at a time) plus one for the prior, when every workgroup of the
-    // launch can be resident at once (n_workgroups chains x g <= CUs) and the solve is a plain body / finger solve.
-    if (coop_g == -1) {
-        const int item_ranks = (Mmax * nkfmax + MOSHII_TPB - 1) / MOSHII_TPB;
-        coop_g = std::min(MOSHII_COOP_MAXG, item_ranks + (npose > 0 ? 1 : 0));
-        if (coop_g < 3 || (!xt && nblk < 4)) coop_g = 0;   // (few items, or a solve so small -- MANO -- that the exchanges cost what the split saves: measured)
-    }
+    int Tm;
+    ChainLayout ly;
+    if (coop_g == -1) coop_g = solve_plan::own_group_size(Mmax, d.nkfmax, npose > 0, !xt && nblk < 4);
     if (coop_g > 0 && ((!xt && nmax + 1 > 8 * 16) || (long long)coop_g * std::max(n_workgroups, 1) > n_cu)) coop_g = 0;   // (not built / not all resident: plain chains)
     if (coop_g > 0) {   // cooperative chains: a rank builds the rows of its own markers only -- one tile of its largest possible share
         if (!xt && nblk < 4) nblk = 4;   // (cooperative instantiations: 4, 5, 7, 8 register blocks; extended variant: 5, 8, 10, 13 as the plain one)
@@ -1078,40 +1079,43 @@ int prepare_launch(moshii_model_t m, moshii_prior_t prior, const moshii_solve_op
         int share = 2;
         for (int r = 0; r < coop_g; ++r) share = std::max(share, mlo[r + 1] - mlo[r]);
         Tm = std::min(40, share + 1);   // (+1: a chain with fewer markers than Mmax rounds its shares on its own)
-        ly = make_layout(m, Mmax, Nvmax, NWmax, npose, G, nmax, nkfmax, Tm, nblk, nhj, nshape);
-        while (Tm > 2 && (size_t)ly.total_doubles * 8 > (size_t)budget) {   // (a share larger than the LDS leaves room for: several tiles per rank)
-            --Tm;
-            ly = make_layout(m, Mmax, Nvmax, NWmax, npose, G, nmax, nkfmax, Tm, nblk, nhj, nshape);
-        }
-        const int NE = nblk * (nblk + 1) / 2, NT = (NE + 3) / 4;
-        // slot: accumulators (2 NT 16-byte units per thread), prior block + gradient ((NE + 2) / 2 units), or 3 M marker coordinates; + 32 granule words
-        cfg->coop_slot_doubles = std::max((4 * NT + 2 * ((NE + 2) / 2)) * MOSHII_TPB, 3 * Mmax + 2) + 32;
+        ly = layout(Tm);
+        while (Tm > 2 && (size_t)ly.total_doubles * 8 > (size_t)budget) ly = layout(--Tm);   // (a share larger than the LDS leaves room for: several tiles per rank)
+        cfg->coop = CoopLayout(nblk, Mmax, coop_g);
         cfg->coop_prior_rank = coop_g - 1;
     } else
     if (const char* e = getenv("MOSHII_TM")) {
         Tm = std::max(1, std::min(40, atoi(e)));
-        ly = make_layout(m, Mmax, Nvmax, NWmax, npose, G, nmax, nkfmax, Tm, nblk, nhj, nshape);
+        ly = layout(Tm);
     } else {
         int best = -1, best_cost = 0;
         for (int t = std::min(40, std::max(2, Mmax)); t >= 2; --t) {
-            const ChainLayout lt = make_layout(m, Mmax, Nvmax, NWmax, npose, G, nmax, nkfmax, t, nblk, nhj, nshape);
+            const ChainLayout lt = layout(t);
             if ((size_t)lt.total_doubles * 8 > (size_t)budget) continue;
             const int full = Mmax / t, rem = Mmax % t;
-            const int rounds = full * ((t * nkfmax + 255) / 256) + (rem ? (rem * nkfmax + 255) / 256 : 0);
+            const int rounds = full * ((t * d.nkfmax + 255) / 256) + (rem ? (rem * d.nkfmax + 255) / 256 : 0);
             const int cost = 3 * rounds + 4 * (full + (rem ? 1 : 0));
             if (best < 0 || cost < best_cost) { best = t; best_cost = cost; }
         }
         if (best < 0) best = 2;   // (does not fit: reported below)
         Tm = best;
-        ly = make_layout(m, Mmax, Nvmax, NWmax, npose, G, nmax, nkfmax, Tm, nblk, nhj, nshape);
+        ly = layout(Tm);
     }
     const size_t lds_bytes = (size_t)ly.total_doubles * sizeof(double);
     if (lds_bytes > 160 * 1024) return fail(MOSHII_ERR_UNSUPPORTED, "problem does not fit the 160 KiB LDS of a CU");
+    cfg->nblk = nblk; cfg->xt = xt; cfg->ly = ly; cfg->lds_bytes = lds_bytes;
+    cfg->coop_g = coop_g;
+    return MOSHII_OK;
+}
 
-    const int njangle = std::max(0, o->n_jangle);
+// prepare_launch, part 3: uploads the id lists to the head of the model's control scratch and fills the option / prior / model
+// descriptors.  `extra_bytes` are reserved behind the id lists; their offset comes back through ctl_off.
+int upload_ids(moshii_model_t m, moshii_prior_t prior, const moshii_solve_opts* o, hipStream_t stream, size_t extra_bytes, LaunchCfg* cfg,
+               size_t* ctl_off) {
+    const int nshape = o->n_shape, njangle = std::max(0, o->n_jangle);
     const size_t nids = (size_t)o->n_step1 + o->n_step2 + o->n_body + o->n_finger + o->n_face + njangle;
     const size_t need = sizeof(int) * (nids + 16) + 64 + extra_bytes;
-    int rc = m->scratch.reserve(need);
+    int rc = m->scratch.reserve(need, stream);
     if (rc) return rc;
     std::vector<int> ids;
     ids.reserve(nids);
@@ -1129,7 +1133,6 @@ int prepare_launch(moshii_model_t m, moshii_prior_t prior, const moshii_solve_op
         HIP_TRY(hipMemcpyAsync(dbase, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice, stream));
         HIP_TRY(hipStreamSynchronize(stream));   // `ids` is pageable and goes out of scope
     }
-    m->scratch.used = true; m->scratch.last_stream = stream;
     *ctl_off = (ids.size() * sizeof(int) + 63) & ~size_t(63);
 
     OptsDev& od = cfg->od;
@@ -1146,76 +1149,131 @@ int prepare_launch(moshii_model_t m, moshii_prior_t prior, const moshii_solve_op
     memset(&cfg->pd, 0, sizeof(cfg->pd));
     if (prior) cfg->pd = prior->dev();
     cfg->md = m->dev();
-    cfg->nblk = nblk; cfg->two_per_cu = xt ? 0 : two_per_cu; cfg->xt = xt; cfg->ly = ly; cfg->lds_bytes = lds_bytes;
-    cfg->coop_g = coop_g;
     return MOSHII_OK;
 }
 
+int prepare_launch(moshii_model_t m, moshii_prior_t prior, const moshii_solve_opts* o, int Mmax, int Nvmax, int NWmax,
+                   int n_workgroups, hipStream_t stream, size_t extra_bytes, LaunchCfg* cfg, size_t* ctl_off, int coop_g = 0) {
+    SolveDims d;
+    int rc;
+    if ((rc = check_opts(m, prior, o, &d))) return rc;
+    if ((rc = choose_layout(m, d, Mmax, Nvmax, NWmax, n_workgroups, coop_g, cfg))) return rc;
+    return upload_ids(m, prior, o, stream, extra_bytes, cfg, ctl_off);
+}
+
 int launch_chains(const LaunchCfg& cfg, int n, const ChainDev* d_chains, hipStream_t stream) {
-    HIP_TRY(moshii_launch_chain_solve(cfg.nblk, cfg.two_per_cu, cfg.xt, n, cfg.lds_bytes, stream, d_chains, &cfg.md, &cfg.pd, &cfg.od, &cfg.ly, cfg.coop_g));
-    g_last.name = "k_chain_solve<" + std::to_string(cfg.nblk) + "," + std::to_string(cfg.two_per_cu ? 2 : 1) + (cfg.xt ? ",xt" : "") +
+    HIP_TRY(moshii_launch_chain_solve(cfg.nblk, cfg.xt, n, cfg.lds_bytes, stream, d_chains, &cfg.md, &cfg.pd, &cfg.od, &cfg.ly, cfg.coop_g));
+    g_last.name = "k_chain_solve<" + std::to_string(cfg.nblk) + ",1" + (cfg.xt ? ",xt" : "") +
                   (cfg.coop_g > 0 ? ",coop" + std::to_string(cfg.coop_g) : "") + ">";
     g_last.lds = (int)cfg.lds_bytes; g_last.threads = MOSHII_TPB;
     return MOSHII_OK;
 }
 
-// host<->device staging of one sequence's per-frame buffers (MOSHII_BUFFERS_HOST callers)
-struct Staged {
-    double *obs = nullptr, *pose = nullptr, *fullpose = nullptr, *trans = nullptr, *msim = nullptr, *errs = nullptr;
-    uint8_t* vis = nullptr;
-    int *iters = nullptr, *status = nullptr;
-    void release() {
-        void* ptrs[] = {obs, vis, pose, fullpose, trans, msim, errs, iters, status};
-        for (void* q : ptrs) if (q) hipFree(q);
-        *this = Staged();
-    }
-};
+// extended variant: a chain's scratch for the shape derivatives of the joint transforms ([2][K][E][3] doubles) and, beyond 8 register
+// blocks, the global packed factor + trash / zero words + a spare word per thread (ldl_big)
+size_t qscratch_bytes(const LaunchCfg& cfg, int K, int E) {
+    const size_t nfac = (cfg.nblk > 8) ? (size_t)(cfg.ly.nmax + 1) * (cfg.ly.nmax + 2) / 2 + 12 + 256 : 0;
+    return ((size_t)2 * K * E * 3 + nfac) * sizeof(double);
+}
 
+// ---- cooperative chains: the exchange buffer kept with the model, laid out by cfg.coop --------------
+int reserve_exchange(moshii_model_t m, const CoopLayout& cl, size_t n_chains, hipStream_t stream) {
+    int rc = m->coopbuf.reserve(cl.bytes_per_chain * n_chains, stream);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(m->coopbuf.ptr, 0, cl.bytes_per_chain * n_chains, stream));   // flags and abort words start at zero on EVERY launch
+    return MOSHII_OK;
+}
+
+void fill_coop(ChainDev& cd, const LaunchCfg& cfg, int M, char* slice) {   // slice: this chain's part of the exchange buffer
+    cd.coop.G = cfg.coop_g; cd.coop.prior_rank = cfg.coop_prior_rank; cd.coop.slot_doubles = cfg.coop.slot_doubles; cd.coop.skew = coop_skew_env();
+    coop_split(M, cfg.coop_g, cfg.coop_prior_frac, cd.coop.mlo);
+    cd.coop.slots = as_gp_rw((unsigned long long*)slice);
+    cd.coop.flags = as_gp_rw((unsigned*)(slice + cfg.coop.flags_offset));
+}
+
+// Did every group of the launch stay whole?  One strided copy of the chains' abort words (a copy per chain was 22 us a chain,
+// 0.5-1 ms a round); synchronises the stream.
+int coop_any_broken(moshii_model_t m, const CoopLayout& cl, size_t n_chains, hipStream_t stream, bool* broken) {
+    std::vector<unsigned> ab(n_chains, 0u);
+    HIP_TRY(hipMemcpy2DAsync(ab.data(), sizeof(unsigned), m->coopbuf.ptr + cl.abort_offset, cl.bytes_per_chain, sizeof(unsigned), n_chains,
+                             hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    *broken = false;
+    for (unsigned a : ab) *broken |= a != 0u;
+    return MOSHII_OK;
+}
+
+// ---- the device buffers a call allocates for itself (MOSHII_BUFFERS_HOST callers; a start state) ----
 struct FrameBufs {   // the per-frame arrays shared by moshii_chain_desc and moshii_sequence_desc
     int F, M;
     const double* obs; const uint8_t* vis;
     double *pose, *fullpose, *trans, *msim, *errs; int *iters, *status;
+    double* shape;   // extended variant: the rows of free shape coefficients (or null)
+};
+struct Staged {   // device copies of one chain's / sequence's per-frame host buffers: freed on every way out
+    FrameBufs rows = {};
+    Staged() = default;
+    Staged(const Staged&) = delete;
+    Staged& operator=(const Staged&) = delete;
+    Staged(Staged&& o) noexcept : rows(o.rows) { o.rows = {}; }
+    Staged& operator=(Staged&& o) noexcept { std::swap(rows, o.rows); return *this; }
+    ~Staged() {
+        const void* ptrs[] = {rows.obs, rows.vis, rows.pose, rows.fullpose, rows.trans, rows.msim, rows.errs, rows.iters, rows.status, rows.shape};
+        for (const void* q : ptrs) if (q) hipFree(const_cast<void*>(q));
+    }
+};
+struct CallBufs {
+    std::vector<Staged> st;      // per chain / sequence; empty for MOSHII_BUFFERS_DEVICE callers
+    double* d_init = nullptr;    // moshii_sequence_solve: start states of the sequences that continue a chain
+    explicit CallBufs(size_t n) : st(n) {}
+    CallBufs(const CallBufs&) = delete;
+    CallBufs& operator=(const CallBufs&) = delete;
+    ~CallBufs() { if (d_init) hipFree(d_init); }
 };
 
-int stage_in(const FrameBufs& h, int NP, int P, hipStream_t stream, Staged* s) {
+template <class T>
+hipError_t dev_zeros(T** out, size_t n, hipStream_t stream) {
+    const hipError_t e = hipMalloc((void**)out, n * sizeof(T));
+    return e != hipSuccess ? e : hipMemsetAsync(*out, 0, n * sizeof(T), stream);
+}
+
+// device copies of the inputs of `h`, zeroed rows for its outputs (n_shape > 0: and that many shape coefficients)
+int stage_in(const FrameBufs& h, int NP, int P, size_t n_shape, hipStream_t stream, Staged* s) {
     const size_t Fz = std::max(h.F, 1), M = h.M;
+    FrameBufs& d = s->rows;
+    d.F = h.F; d.M = h.M;
     int rc;
-    if ((rc = dev_upload(h.obs, (size_t)h.F * M * 3, &s->obs))) return rc;
-    if ((rc = dev_upload(h.vis, (size_t)h.F * M, &s->vis))) return rc;
-    HIP_TRY(hipMalloc((void**)&s->pose, Fz * NP * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&s->fullpose, Fz * P * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&s->trans, Fz * 3 * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&s->msim, Fz * M * 3 * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&s->errs, Fz * MOSHII_NERR * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&s->iters, Fz * 2 * sizeof(int)));
-    HIP_TRY(hipMalloc((void**)&s->status, Fz * sizeof(int)));
-    HIP_TRY(hipMemsetAsync(s->pose, 0, Fz * NP * sizeof(double), stream));
-    HIP_TRY(hipMemsetAsync(s->fullpose, 0, Fz * P * sizeof(double), stream));
-    HIP_TRY(hipMemsetAsync(s->trans, 0, Fz * 3 * sizeof(double), stream));
-    HIP_TRY(hipMemsetAsync(s->msim, 0, Fz * M * 3 * sizeof(double), stream));
-    HIP_TRY(hipMemsetAsync(s->errs, 0, Fz * MOSHII_NERR * sizeof(double), stream));
-    HIP_TRY(hipMemsetAsync(s->iters, 0, Fz * 2 * sizeof(int), stream));
-    HIP_TRY(hipMemsetAsync(s->status, 0, Fz * sizeof(int), stream));
+    if ((rc = dev_upload(h.obs, (size_t)h.F * M * 3, const_cast<double**>(&d.obs)))) return rc;
+    if ((rc = dev_upload(h.vis, (size_t)h.F * M, const_cast<uint8_t**>(&d.vis)))) return rc;
+    HIP_TRY(dev_zeros(&d.pose, Fz * NP, stream));
+    HIP_TRY(dev_zeros(&d.fullpose, Fz * P, stream));
+    HIP_TRY(dev_zeros(&d.trans, Fz * 3, stream));
+    HIP_TRY(dev_zeros(&d.msim, Fz * M * 3, stream));
+    HIP_TRY(dev_zeros(&d.errs, Fz * MOSHII_NERR, stream));
+    HIP_TRY(dev_zeros(&d.iters, Fz * 2, stream));
+    HIP_TRY(dev_zeros(&d.status, Fz, stream));
+    if (n_shape > 0) HIP_TRY(dev_zeros(&d.shape, n_shape, stream));
     return MOSHII_OK;
 }
 
-int stage_out(const FrameBufs& h, int NP, int P, Staged* s) {
+// copies the results back (the stream has been synchronised); `s` frees the device copies when it goes
+int stage_out(const FrameBufs& h, int NP, int P, int E, const Staged& s) {
     const size_t F = h.F, M = h.M;
-    if (F) {
-        if (h.pose) HIP_TRY(hipMemcpy(h.pose, s->pose, F * NP * sizeof(double), hipMemcpyDeviceToHost));
-        if (h.fullpose) HIP_TRY(hipMemcpy(h.fullpose, s->fullpose, F * P * sizeof(double), hipMemcpyDeviceToHost));
-        if (h.trans) HIP_TRY(hipMemcpy(h.trans, s->trans, F * 3 * sizeof(double), hipMemcpyDeviceToHost));
-        if (h.msim) HIP_TRY(hipMemcpy(h.msim, s->msim, F * M * 3 * sizeof(double), hipMemcpyDeviceToHost));
-        if (h.errs) HIP_TRY(hipMemcpy(h.errs, s->errs, F * MOSHII_NERR * sizeof(double), hipMemcpyDeviceToHost));
-        if (h.iters) HIP_TRY(hipMemcpy(h.iters, s->iters, F * 2 * sizeof(int), hipMemcpyDeviceToHost));
-        if (h.status) HIP_TRY(hipMemcpy(h.status, s->status, F * sizeof(int), hipMemcpyDeviceToHost));
-    }
-    s->release();
+    const FrameBufs& d = s.rows;
+    if (!F) return MOSHII_OK;
+    if (h.pose) HIP_TRY(hipMemcpy(h.pose, d.pose, F * NP * sizeof(double), hipMemcpyDeviceToHost));
+    if (h.fullpose) HIP_TRY(hipMemcpy(h.fullpose, d.fullpose, F * P * sizeof(double), hipMemcpyDeviceToHost));
+    if (h.trans) HIP_TRY(hipMemcpy(h.trans, d.trans, F * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (h.msim) HIP_TRY(hipMemcpy(h.msim, d.msim, F * M * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (h.errs) HIP_TRY(hipMemcpy(h.errs, d.errs, F * MOSHII_NERR * sizeof(double), hipMemcpyDeviceToHost));
+    if (h.iters) HIP_TRY(hipMemcpy(h.iters, d.iters, F * 2 * sizeof(int), hipMemcpyDeviceToHost));
+    if (h.status) HIP_TRY(hipMemcpy(h.status, d.status, F * sizeof(int), hipMemcpyDeviceToHost));
+    if (h.shape && d.shape) HIP_TRY(hipMemcpy(h.shape, d.shape, F * E * sizeof(double), hipMemcpyDeviceToHost));
     return MOSHII_OK;
 }
 
-// max |entry_c - final_pred(c)| per chunk (pose, trans, and pose_prev when the velocity term is live); a flag
-// mismatch (first-frame schedule pending / velocity term missing on one side) counts as infinite deviation.
+// max |entry_c - final_pred(c)| per chunk (pose, trans, and pose_prev when the velocity term is live), or one of the verdicts
+// MOSHII_HANDOFF_* (solve_plan.h) where the states cannot be compared.
 __global__ void k_verify_chunks(int n, int NP, int E, const int* __restrict__ pred, const double* __restrict__ entry,
                                 const double* __restrict__ fin, double* __restrict__ dev) {
     const int c = blockIdx.x;
@@ -1241,10 +1299,10 @@ __global__ void k_verify_chunks(int n, int NP, int E, const int* __restrict__ pr
             nan |= !(v == v);
             d = fmax(d, v);
         }
-        if (nan) d = 2e300;          // a NaN state: reported as MOSHII_ERR_NUMERIC by the caller
-        else if (a[2 * NP + 3] == -1.0 && b[2 * NP + 3] != -2.0) d = 5e299;   // this chunk's pass-1 chain gave the chunk up (ChainDev::tail_done): re-solve it, nothing else is wrong
-        else if (b[2 * NP + 3] == -2.0) d = 4e299;                             // the predecessor was given up: its sweep hands over at the boundary
-        else if (!flags_ok) d = 1e300;
+        if (nan) d = MOSHII_HANDOFF_NAN;
+        else if (a[2 * NP + 3] == MOSHII_MARK_ENTRY_SPOILED && b[2 * NP + 3] != MOSHII_MARK_FINAL_SPOILED) d = MOSHII_HANDOFF_GIVEN_UP;
+        else if (b[2 * NP + 3] == MOSHII_MARK_FINAL_SPOILED) d = MOSHII_HANDOFF_PRED_GIVEN_UP;
+        else if (!flags_ok) d = MOSHII_HANDOFF_MISMATCH;
     }
     red[threadIdx.x] = d;
     __syncthreads();
@@ -1252,14 +1310,12 @@ __global__ void k_verify_chunks(int n, int NP, int E, const int* __restrict__ pr
     if (threadIdx.x == 0) dev[c] = red[0];
 }
 
-}  // namespace
-
-extern "C" {
-
-int moshii_chain_solve(moshii_model_t m, moshii_prior_t prior, const moshii_solve_opts* o, int32_t n_chains,
-                       const moshii_chain_desc* chains, uint32_t flags, void* stream_) {
-    if (!m || !o || !chains || n_chains < 1) return fail(MOSHII_ERR_ARG, "bad argument");
-    hipStream_t stream = (hipStream_t)stream_;
+// ---- moshii_chain_solve ------------------------------------------------------------------------------
+// One launch of the chains.  *broken: a cooperative group broke up -- a workgroup of it did not show up within the wait limit (the chip
+// is shared with another process?) -- and the caller repeats the solve with plain chains.
+int chain_solve_once(moshii_model_t m, moshii_prior_t prior, const moshii_solve_opts* o, int32_t n_chains, const moshii_chain_desc* chains,
+                     uint32_t flags, hipStream_t stream, bool* broken) {
+    *broken = false;
     const bool dev = (flags & MOSHII_BUFFERS_DEVICE) != 0;
     const int NP = m->NP, P = m->P;
     int Mmax = 0, Nvmax = 0, NWmax = 1;
@@ -1279,40 +1335,23 @@ int moshii_chain_solve(moshii_model_t m, moshii_prior_t prior, const moshii_solv
     int rc = prepare_launch(m, prior, o, Mmax, Nvmax, NWmax, n_chains, stream, extra, &cfg, &ctl, coop_req);
     if (rc) return rc;
     const int coop_g = cfg.coop_g;   // (0: plain chains -- asked for, or the group does not fit the chip / the solve is an extended one)
-    size_t coop_bytes_per_chain = 0;
-    if (coop_g > 0) {
-        coop_bytes_per_chain = ((size_t)2 * coop_g * cfg.coop_slot_doubles * sizeof(unsigned long long) + (size_t)(2 * coop_g + 2) * sizeof(unsigned) + 255) & ~size_t(255);
-        if ((rc = m->coopbuf.reserve(coop_bytes_per_chain * n_chains))) return rc;
-        m->coopbuf.used = true; m->coopbuf.last_stream = stream;
-        HIP_TRY(hipMemsetAsync(m->coopbuf.ptr, 0, coop_bytes_per_chain * n_chains, stream));   // flags and abort words start at zero on EVERY call
-    }
+    if (coop_g > 0 && (rc = reserve_exchange(m, cfg.coop, n_chains, stream))) return rc;
     char* dbase = m->scratch.ptr + ctl;
-    // extended variant: per-chain scratch for the shape derivatives of the joint transforms ([2][K][E][3] doubles)
-    const size_t nfac = (cfg.nblk > 8) ? (size_t)(cfg.ly.nmax + 1) * (cfg.ly.nmax + 2) / 2 + 12 + 256 : 0;   // global packed factor + trash / zero words + a spare word per thread (ldl_big)
-    const size_t qbytes = ((size_t)2 * m->K * E * 3 + nfac) * sizeof(double);
+    const size_t qbytes = qscratch_bytes(cfg, m->K, E);
     const int qranks = (coop_g > 0) ? coop_g : 1;   // (cooperative chains: a slice per rank -- every rank keeps its own derivative arrays / factor)
-    if (E > 0) {
-        if ((rc = m->qscratch.reserve(qbytes * n_chains * qranks))) return rc;
-        m->qscratch.used = true; m->qscratch.last_stream = stream;
-    }
-    std::vector<double*> d_shape(n_chains, nullptr);
+    if (E > 0 && (rc = m->qscratch.reserve(qbytes * n_chains * qranks, stream))) return rc;
     std::vector<char> hostbuf(extra, 0);
     size_t off = sizeof(ChainDev) * n_chains;
     auto put = [&](const void* src, size_t bytes) { off = (off + 15) & ~size_t(15); size_t o2 = off; memcpy(hostbuf.data() + off, src, bytes); off += bytes; return o2; };
-    std::vector<Staged> st(dev ? 0 : n_chains);
+    CallBufs bufs(dev ? 0 : n_chains);
+    std::vector<FrameBufs> fbs(n_chains);
     std::vector<ChainDev> cds(n_chains);
     for (int c = 0; c < n_chains; ++c) {
         const moshii_chain_desc& ch = chains[c];
         ChainDev& cd = cds[c];
         memset(&cd, 0, sizeof(cd));
         cd.att = ch.attach->d_self; cd.F = ch.F; cd.first = ch.first_frame_schedule;
-        if (coop_g > 0) {
-            cd.coop.G = coop_g; cd.coop.prior_rank = cfg.coop_prior_rank; cd.coop.slot_doubles = cfg.coop_slot_doubles; cd.coop.skew = coop_skew_env();
-            coop_split(ch.attach->M, coop_g, cfg.coop_prior_frac, cd.coop.mlo);
-            char* cb = m->coopbuf.ptr + coop_bytes_per_chain * c;
-            cd.coop.slots = as_gp_rw((unsigned long long*)cb);
-            cd.coop.flags = as_gp_rw((unsigned*)(cb + (size_t)2 * coop_g * cfg.coop_slot_doubles * sizeof(unsigned long long)));
-        }
+        if (coop_g > 0) fill_coop(cd, cfg, ch.attach->M, m->coopbuf.ptr + cfg.coop.bytes_per_chain * c);
         if (ch.init_pose) cd.init_pose = (const double*)(dbase + put(ch.init_pose, sizeof(double) * NP));
         if (ch.init_trans) cd.init_trans = (const double*)(dbase + put(ch.init_trans, sizeof(double) * 3));
         if (ch.init_pose_prev) cd.init_prev = (const double*)(dbase + put(ch.init_pose_prev, sizeof(double) * NP));
@@ -1321,168 +1360,113 @@ int moshii_chain_solve(moshii_model_t m, moshii_prior_t prior, const moshii_solv
             cd.qscratch = (double*)(m->qscratch.ptr + qbytes * (size_t)c * qranks);
             cd.coop.qstride = (int)(qbytes / sizeof(double));
         }
-        if (dev) {
-            cd.obs = ch.obs; cd.vis = ch.vis; cd.pose = ch.pose; cd.fullpose = ch.fullpose; cd.trans = ch.trans;
-            cd.msim = ch.markers_sim; cd.errs = ch.errs; cd.iters = ch.iters; cd.status = ch.status;
-            cd.shape = E > 0 ? ch.shape : nullptr;
-        } else {
-            if (E > 0 && ch.shape && ch.F > 0) {
-                HIP_TRY(hipMalloc((void**)&d_shape[c], (size_t)ch.F * E * sizeof(double)));
-                HIP_TRY(hipMemsetAsync(d_shape[c], 0, (size_t)ch.F * E * sizeof(double), stream));
-                cd.shape = d_shape[c];
-            }
-            const FrameBufs fb{ch.F, ch.attach->M, ch.obs, ch.vis, ch.pose, ch.fullpose, ch.trans, ch.markers_sim, ch.errs, ch.iters, ch.status};
-            Staged& s = st[c];
-            if ((rc = stage_in(fb, NP, P, stream, &s))) return rc;
-            cd.obs = s.obs; cd.vis = s.vis; cd.pose = s.pose; cd.fullpose = s.fullpose; cd.trans = s.trans;
-            cd.msim = s.msim; cd.errs = s.errs; cd.iters = s.iters; cd.status = s.status;
-        }
+        fbs[c] = FrameBufs{ch.F, ch.attach->M, ch.obs, ch.vis, ch.pose, ch.fullpose, ch.trans, ch.markers_sim, ch.errs, ch.iters, ch.status, E > 0 ? ch.shape : nullptr};
+        if (!dev && (rc = stage_in(fbs[c], NP, P, (fbs[c].shape && ch.F > 0) ? (size_t)ch.F * E : 0, stream, &bufs.st[c]))) return rc;
+        const FrameBufs& b = dev ? fbs[c] : bufs.st[c].rows;   // where the chain finds its rows
+        cd.obs = b.obs; cd.vis = b.vis; cd.pose = b.pose; cd.fullpose = b.fullpose; cd.trans = b.trans;
+        cd.msim = b.msim; cd.errs = b.errs; cd.iters = b.iters; cd.status = b.status; cd.shape = b.shape;
     }
     if (off > extra) return fail(MOSHII_ERR_ARG, "internal: scratch overflow");
     memcpy(hostbuf.data(), cds.data(), sizeof(ChainDev) * n_chains);
     HIP_TRY(hipMemcpyAsync(dbase, hostbuf.data(), off, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipStreamSynchronize(stream));   // hostbuf is pageable and goes out of scope
     if ((rc = launch_chains(cfg, n_chains, (const ChainDev*)dbase, stream))) return rc;
-    if (coop_g > 0) {   // did every group stay whole?  (the call synchronises: a broken group has to be reported, not left in the rows)
-        std::vector<unsigned> ab(n_chains, 0u);   // (one strided copy for all chains)
-        HIP_TRY(hipMemcpy2DAsync(ab.data(), sizeof(unsigned), m->coopbuf.ptr + (size_t)2 * coop_g * cfg.coop_slot_doubles * sizeof(unsigned long long) + coop_g * sizeof(unsigned),
-                                 coop_bytes_per_chain, sizeof(unsigned), (size_t)n_chains, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        bool broken = false;
-        for (int c = 0; c < n_chains; ++c) broken |= ab[c] != 0u;
-        if (broken) {
-            // a workgroup of a group did not show up within the wait limit (the chip is shared with another process?): the same solve as
-            // plain chains, over whatever the broken groups left in the rows
-            note_coop_broken("moshii_chain_solve");
-            if (!dev) for (int c = 0; c < n_chains; ++c) { st[c].release(); if (d_shape[c]) hipFree(d_shape[c]); }
-            return moshii_chain_solve(m, prior, o, n_chains, chains, (flags & ~0xff00u) | (1u << 8), stream_);
-        }
+    // (the call synchronises: a broken group has to be reported, not left in the rows)
+    if (coop_g > 0) {
+        if ((rc = coop_any_broken(m, cfg.coop, n_chains, stream, broken))) return rc;
+        if (*broken) return MOSHII_OK;
     }
     if (!dev) {
         HIP_TRY(hipStreamSynchronize(stream));
-        for (int c = 0; c < n_chains; ++c) {
-            const moshii_chain_desc& ch = chains[c];
-            const FrameBufs fb{ch.F, ch.attach->M, ch.obs, ch.vis, ch.pose, ch.fullpose, ch.trans, ch.markers_sim, ch.errs, ch.iters, ch.status};
-            if ((rc = stage_out(fb, NP, P, &st[c]))) return rc;
-            if (d_shape[c]) {
-                HIP_TRY(hipMemcpy(ch.shape, d_shape[c], (size_t)ch.F * E * sizeof(double), hipMemcpyDeviceToHost));
-                hipFree(d_shape[c]);
-            }
-        }
+        for (int c = 0; c < n_chains; ++c)
+            if ((rc = stage_out(fbs[c], NP, P, E, bufs.st[c]))) return rc;
     }
     return MOSHII_OK;
 }
 
-int moshii_plan_chunks(int32_t F, int32_t num_chunks, int32_t warmup, int32_t cap, int32_t* starts, int32_t* launch_starts) {
-    if (F < 0 || num_chunks < 1 || warmup < 0 || cap < 1 || !starts || !launch_starts) return fail(MOSHII_ERR_ARG, "bad argument");
-    int C = std::min<int64_t>(num_chunks, std::max(F, 1));
-    C = std::min(C, cap);
-    for (int c = 0; c < C; ++c) {
-        starts[c] = (int32_t)(((int64_t)F * c) / C);                 // balanced: lengths differ by at most one frame
-        launch_starts[c] = (c == 0) ? 0 : std::max(0, starts[c] - warmup);
-    }
-    return C;
-}
-
-int moshii_sequence_solve(moshii_model_t m, moshii_prior_t prior, const moshii_solve_opts* o, int32_t n_seq,
-                          const moshii_sequence_desc* seqs, const moshii_chunk_opts* co, uint32_t flags, void* stream_,
-                          moshii_chunk_report* report) {
-    if (!m || !o || !seqs || n_seq < 1) return fail(MOSHII_ERR_ARG, "bad argument");
-    hipStream_t stream = (hipStream_t)stream_;
+// ---- moshii_sequence_solve, step by step: plan, prepare, stage, launch_pass1, { verify, solve_plan::pick_repairs, repair_round }, finish ----
+struct SeqSolve {
+    const moshii_model_t m; const moshii_prior_t prior; const moshii_solve_opts* const o;
+    const int n_seq; const moshii_sequence_desc* const seqs; const moshii_chunk_opts* const co; const uint32_t flags; const hipStream_t stream;
     const bool dev = (flags & MOSHII_BUFFERS_DEVICE) != 0;
     const int NP = m->NP, P = m->P, E = o->n_shape, S = 2 * NP + 5 + E;   // hand-off state: [pose][pose_prev][trans][has_prev][first][shape]
-    if (E > 0 && E != m->nshape) return fail(MOSHII_ERR_ARG, "n_shape does not match moshii_model_set_free_shape");
     const int warmup = co ? std::max(0, co->warmup) : 32;
     const double tol = (co && co->verify_tol > 0.0) ? co->verify_tol : 1e-11;
     const bool rejoin = getenv("MOSHII_NO_REJOIN") == nullptr;   // repair chains stop where they re-join the stored trajectory
-    int Mmax = 0, Nvmax = 0, NWmax = 1;
-    int64_t Ftot = 0;
-    for (int q = 0; q < n_seq; ++q) {
-        const moshii_sequence_desc& sq = seqs[q];
-        if (!sq.attach || sq.attach->model != m || sq.F < 0 || !sq.obs || !sq.vis) return fail(MOSHII_ERR_ARG, "bad sequence descriptor");
-        Mmax = std::max(Mmax, sq.attach->M); Nvmax = std::max(Nvmax, sq.attach->Nv); NWmax = std::max(NWmax, sq.attach->NW);
-        Ftot += sq.F;
-    }
-    // ---- chunk plan
-    int n_cu = 256;
-    { int d = 0; hipGetDevice(&d); hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, d); if (n_cu < 1) n_cu = 256; }
-    int want_total = co ? co->num_chunks : 0;   // chunks per sequence when > 0
-    struct Chunk { int seq, s, e, a, pred; };
+    int Mmax = 0, Nvmax = 0, NWmax = 1, n_cu = 256, NC = 0;
     std::vector<Chunk> chunks;
-    {
-        const int min_len = std::max(4, warmup / 2);
-        const int64_t slots = n_cu;   // one workgroup per CU (see prepare_launch)
-        std::vector<int32_t> st, ls;
-        for (int q = 0; q < n_seq; ++q) {
-            const int F = seqs[q].F;
-            int C = want_total;
-            if (C <= 0) {   // auto: fill the chip once, but keep chunks at least min_len frames long
-                const int64_t share = std::max<int64_t>(1, (slots * F) / std::max<int64_t>(Ftot, 1));
-                C = (int)std::max<int64_t>(1, std::min<int64_t>(share, F / min_len));
-            }
-            st.assign(std::max(C, 1), 0); ls.assign(std::max(C, 1), 0);
-            C = moshii_plan_chunks(F, C, warmup, 1 << 20, st.data(), ls.data());
-            if (C < 0) return C;
-            for (int c = 0; c < C; ++c) {
-                Chunk ck; ck.seq = q; ck.s = st[c]; ck.e = (c + 1 < C) ? st[c + 1] : F; ck.a = ls[c];
-                ck.pred = (c == 0) ? -1 : (int)chunks.size() - 1;
-                chunks.push_back(ck);
-            }
-        }
-    }
-    const int NC = (int)chunks.size();
-    // ---- launch preparation + control block: [ChainDev x NC (pass 1)][ChainDev x NC (repairs)][pred x NC]
-    const size_t extra = 2 * sizeof(ChainDev) * NC + 10 * sizeof(int) * NC + 256;
     LaunchCfg cfg;
-    size_t ctl = 0;
-    int rc = prepare_launch(m, prior, o, Mmax, Nvmax, NWmax, NC, stream, extra, &cfg, &ctl);
-    if (rc) return rc;
-    char* dbase = m->scratch.ptr + ctl;
-    ChainDev* d_pass1 = (ChainDev*)dbase;
-    ChainDev* d_repair = d_pass1 + NC;
-    int* d_pred = (int*)(d_repair + NC);
-    int* d_bnd = d_pred + NC;   // first frame of every chunk (the boundaries a run-through repair chain crosses)
-    int* d_done = d_bnd + NC;   // frames processed per repair chain (diagnostics)
-    int* d_baton = d_done + NC; // [2 NC] state / stop request per chunk (ChainDev::baton)
-    int* d_abort_at = d_baton + 2 * NC;   // [NC] ChainDev::abort_at (kept across the rounds of this call)
-    int* d_fuse = d_abort_at + NC;        // [3 NC] ChainDev::fuse_flags, then [1] ChainDev::fuse_count
-    int* d_fuse_count = d_fuse + 3 * NC;
-    // Pass-1 chains check their own right-hand hand-off and carry on as the repair chain of the next chunk when it misses
-    // (ChainDev::fuse_F): possible when every chunk has a CU of its own for the whole launch, so that the flags they wait on are set.
-    // Cooperative repair chains (MOSHII_COOP_GROUP(g) in `flags`, or MOSHII_COOP_REPAIR=g): the sweeps that bound a chunked solve run with g
-    // workgroups each (csrc/moshii_dev.h: CoopDev), launched by the host's rounds -- a pass-1 chain cannot recruit CUs, so with them the
-    // chains do not carry on inside the first launch.
-    int coop_rep = coop_request(flags, "MOSHII_COOP_REPAIR");
-    if (coop_rep < -1) return fail(MOSHII_ERR_ARG, "cooperative chains: group size out of range");
-    if (coop_rep == -1) {   // the library's choice: as moshii_chain_solve picks it for one chain (prepare_launch)
-        const int item_ranks = (Mmax * cfg.ly.nkfmax + MOSHII_TPB - 1) / MOSHII_TPB;
-        coop_rep = std::min(MOSHII_COOP_MAXG, item_ranks + ((prior && o->n_body > 0) ? 1 : 0));
-        if (coop_rep < 3 || cfg.ly.nmax + 1 > 8 * 16 || cfg.nblk < 4) coop_rep = 0;
+    size_t ctl = 0, extra = 0;   // the control block behind the id lists (prepare)
+    ChainDev *d_pass1 = nullptr, *d_repair = nullptr;
+    int *d_pred = nullptr, *d_bnd = nullptr, *d_done = nullptr, *d_baton = nullptr, *d_abort_at = nullptr, *d_fuse = nullptr, *d_fuse_count = nullptr;
+    double *d_entry = nullptr, *d_final = nullptr, *d_dev = nullptr;   // hand-off states [NC][S] x 2 and deviations [NC]
+    int coop_rep = 0;            // workgroups per repair chain (0: plain chains)
+    bool fuse = false, trace = false;
+    std::vector<LaunchCfg> coop_cfgs = std::vector<LaunchCfg>(MOSHII_COOP_MAXG + 1);   // per group size, prepared when first used (coop_g set)
+    CallBufs bufs{dev ? (size_t)0 : (size_t)n_seq};   // the device buffers of this call: released on EVERY way out of it
+    std::vector<FrameBufs> fbs, dbs;                  // the caller's rows; where the chains find them on the device
+    size_t qbytes = 0;
+    std::vector<double> hdev;    // the last verification's hand-off deviations / verdicts
+    int n_repaired = 0, rounds = 0;
+
+    int plan() {
+        std::vector<int> frames(n_seq);
+        for (int q = 0; q < n_seq; ++q) {
+            const moshii_sequence_desc& sq = seqs[q];
+            if (!sq.attach || sq.attach->model != m || sq.F < 0 || !sq.obs || !sq.vis) return fail(MOSHII_ERR_ARG, "bad sequence descriptor");
+            Mmax = std::max(Mmax, sq.attach->M); Nvmax = std::max(Nvmax, sq.attach->Nv); NWmax = std::max(NWmax, sq.attach->NW);
+            frames[q] = sq.F;
+        }
+        n_cu = cu_count();
+        chunks = solve_plan::chunk_table(frames, co ? co->num_chunks : 0, warmup, n_cu);   // (num_chunks: chunks per sequence when > 0)
+        NC = (int)chunks.size();
+        return MOSHII_OK;
     }
-    if (coop_rep < 2 || E > 0 || o->n_face > 0 || !rejoin) coop_rep = 0;
-    const bool fuse = rejoin && NC <= n_cu && getenv("MOSHII_NO_FUSE") == nullptr && coop_rep == 0;
-    const bool trace = getenv("MOSHII_TRACE_REPAIR") != nullptr;
-    std::vector<LaunchCfg> coop_cfgs(MOSHII_COOP_MAXG + 1);   // per group size, prepared when first used
-    std::vector<char> coop_cfg_ready(MOSHII_COOP_MAXG + 1, 0);
-    if (coop_rep >= 2) {
-        // the exchange buffers of the repair rounds, once and for the largest round this call can launch (a buffer that grows from
-        // round to round is a hipFree + hipMalloc in the middle of the solve)
-        const int nb = std::max(4, cfg.nblk), NEc = nb * (nb + 1) / 2, NTc = (NEc + 3) / 4;
-        const size_t slot = (size_t)std::max((4 * NTc + 2 * ((NEc + 2) / 2)) * MOSHII_TPB, 3 * Mmax + 2) + 32;
-        const size_t per = ((size_t)2 * coop_rep * slot * sizeof(unsigned long long) + (size_t)(2 * coop_rep + 2) * sizeof(unsigned) + 255) & ~size_t(255);
-        if ((rc = m->coopbuf.reserve(per * (size_t)std::min(NC, std::max(1, n_cu / 2))))) return rc;
+
+    // The launch configuration, the control block [ChainDev x NC (pass 1)][ChainDev x NC (repairs)][control words x 10 NC + 1], how the
+    // repairs run (carried on inside the first launch / plain rounds / cooperative rounds) and the buffers kept with the model.
+    int prepare() {
+        extra = 2 * sizeof(ChainDev) * NC + 10 * sizeof(int) * NC + 256;
+        int rc = prepare_launch(m, prior, o, Mmax, Nvmax, NWmax, NC, stream, extra, &cfg, &ctl);
+        if (rc) return rc;
+        d_pass1 = (ChainDev*)(m->scratch.ptr + ctl);
+        d_repair = d_pass1 + NC;
+        d_pred = (int*)(d_repair + NC);
+        d_bnd = d_pred + NC;   // first frame of every chunk (the boundaries a run-through repair chain crosses)
+        d_done = d_bnd + NC;   // frames processed per repair chain (diagnostics)
+        d_baton = d_done + NC; // [2 NC] state / stop request per chunk (ChainDev::baton)
+        d_abort_at = d_baton + 2 * NC;   // [NC] ChainDev::abort_at (kept across the rounds of this call)
+        d_fuse = d_abort_at + NC;        // [3 NC] ChainDev::fuse_flags, then [1] ChainDev::fuse_count
+        d_fuse_count = d_fuse + 3 * NC;
+        // Pass-1 chains check their own right-hand hand-off and carry on as the repair chain of the next chunk when it misses
+        // (ChainDev::fuse_F): possible when every chunk has a CU of its own for the whole launch, so that the flags they wait on are set.
+        // Cooperative repair chains (MOSHII_COOP_GROUP(g) in `flags`, or MOSHII_COOP_REPAIR=g): the sweeps that bound a chunked solve run with g
+        // workgroups each (csrc/moshii_dev.h: CoopDev), launched by the host's rounds -- a pass-1 chain cannot recruit CUs, so with them the
+        // chains do not carry on inside the first launch.
+        coop_rep = coop_request(flags, "MOSHII_COOP_REPAIR");
+        if (coop_rep < -1) return fail(MOSHII_ERR_ARG, "cooperative chains: group size out of range");
+        if (coop_rep == -1)   // the library's choice: as moshii_chain_solve picks it for one chain (choose_layout)
+            coop_rep = solve_plan::own_group_size(Mmax, cfg.ly.nkfmax, prior && o->n_body > 0, cfg.ly.nmax + 1 > 8 * 16 || cfg.nblk < 4);
+        if (coop_rep < 2 || E > 0 || o->n_face > 0 || !rejoin) coop_rep = 0;
+        fuse = rejoin && NC <= n_cu && getenv("MOSHII_NO_FUSE") == nullptr && coop_rep == 0;
+        trace = getenv("MOSHII_TRACE_REPAIR") != nullptr;
+        if (coop_rep >= 2) {
+            // the exchange buffers of the repair rounds, once and for the largest round this call can launch (a buffer that grows from
+            // round to round is a hipFree + hipMalloc in the middle of the solve)
+            const CoopLayout largest(std::max(4, cfg.nblk), Mmax, coop_rep);
+            if ((rc = m->coopbuf.reserve(largest.bytes_per_chain * (size_t)std::min(NC, std::max(1, n_cu / 2))))) return rc;
+        }
+        // (kept with the model between calls: three hipMalloc / hipFree pairs a call were ~0.3 ms of a 37 ms step)
+        if ((rc = m->handoff.reserve(((size_t)2 * NC * S + NC) * sizeof(double), stream))) return rc;
+        d_entry = (double*)m->handoff.ptr;
+        d_final = d_entry + (size_t)NC * S;
+        d_dev = d_final + (size_t)NC * S;
+        return MOSHII_OK;
     }
-    // device buffers of this call: released on EVERY way out of the function (error returns included)
-    struct Owned { std::vector<void*> p; ~Owned() { for (void* q : p) if (q) hipFree(q); } } owned;
-    // (kept with the model between calls: three hipMalloc / hipFree pairs a call were ~0.3 ms of a 37 ms step)
-    if ((rc = m->handoff.reserve(((size_t)2 * NC * S + NC) * sizeof(double)))) return rc;
-    m->handoff.used = true; m->handoff.last_stream = stream;
-    double* d_entry = (double*)m->handoff.ptr;
-    double* d_final = d_entry + (size_t)NC * S;
-    double* d_dev = d_final + (size_t)NC * S;
-    // start states of sequences that continue a chain (moshii_sequence_desc.init_*): [pose][pose_prev][trans][has_prev][first = 0]
-    double* d_init = nullptr;
-    {
+
+    int stage() {
+        int rc;
+        // start states of sequences that continue a chain (moshii_sequence_desc.init_*): [pose][pose_prev][trans][has_prev][first = 0]
         bool any = false;
         for (int q = 0; q < n_seq; ++q) any |= seqs[q].init_pose != nullptr;
         if (any) {
@@ -1499,44 +1483,25 @@ int moshii_sequence_solve(moshii_model_t m, moshii_prior_t prior, const moshii_s
                 h[2 * NP + 4] = 0.0;
                 if (E > 0 && sq.init_shape) memcpy(h + 2 * NP + 5, sq.init_shape, sizeof(double) * E);
             }
-            HIP_TRY(hipMalloc((void**)&d_init, hinit.size() * sizeof(double))); owned.p.push_back(d_init);
-            HIP_TRY(hipMemcpy(d_init, hinit.data(), hinit.size() * sizeof(double), hipMemcpyHostToDevice));
+            HIP_TRY(hipMalloc((void**)&bufs.d_init, hinit.size() * sizeof(double)));
+            HIP_TRY(hipMemcpy(bufs.d_init, hinit.data(), hinit.size() * sizeof(double), hipMemcpyHostToDevice));
         }
-    }
-    auto cleanup = [&]() {};   // (buffers are released by `owned`)
-    std::vector<Staged> st(dev ? 0 : n_seq);
-    std::vector<FrameBufs> fbs(n_seq), dbs(n_seq);
-    for (int q = 0; q < n_seq; ++q) {
-        const moshii_sequence_desc& sq = seqs[q];
-        fbs[q] = FrameBufs{sq.F, sq.attach->M, sq.obs, sq.vis, sq.pose, sq.fullpose, sq.trans, sq.markers_sim, sq.errs, sq.iters, sq.status};
-        dbs[q] = fbs[q];
-        if (!dev) {
-            Staged& s = st[q];
-            if ((rc = stage_in(fbs[q], NP, P, stream, &s))) { cleanup(); return rc; }
-            dbs[q].obs = s.obs; dbs[q].vis = s.vis; dbs[q].pose = s.pose; dbs[q].fullpose = s.fullpose; dbs[q].trans = s.trans;
-            dbs[q].msim = s.msim; dbs[q].errs = s.errs; dbs[q].iters = s.iters; dbs[q].status = s.status;
-        }
-    }
-    // extended variant: per-sequence shape rows (device) and per-chain scratch for the shape derivatives of the joint transforms
-    std::vector<double*> shp(n_seq, nullptr);
-    std::vector<char> shp_owned(n_seq, 0);
-    size_t qbytes = 0;
-    auto cleanup_shape = [&]() {};   // (released by `owned`)
-    if (E > 0) {
-        const size_t nfac = (cfg.nblk > 8) ? (size_t)(cfg.ly.nmax + 1) * (cfg.ly.nmax + 2) / 2 + 12 + 256 : 0;
-        qbytes = ((size_t)2 * m->K * E * 3 + nfac) * sizeof(double);
-        if ((rc = m->qscratch.reserve(qbytes * NC))) { cleanup(); return rc; }
-        m->qscratch.used = true; m->qscratch.last_stream = stream;
+        fbs.resize(n_seq); dbs.resize(n_seq);
         for (int q = 0; q < n_seq; ++q) {
-            if (dev) { shp[q] = seqs[q].shape; continue; }
-            if (seqs[q].F < 1) continue;
-            if (hipMalloc((void**)&shp[q], (size_t)seqs[q].F * E * sizeof(double)) != hipSuccess) return fail(MOSHII_ERR_HIP, "hipMalloc failed");
-            shp_owned[q] = 1; owned.p.push_back(shp[q]);
-            hipMemsetAsync(shp[q], 0, (size_t)seqs[q].F * E * sizeof(double), stream);
+            const moshii_sequence_desc& sq = seqs[q];
+            fbs[q] = FrameBufs{sq.F, sq.attach->M, sq.obs, sq.vis, sq.pose, sq.fullpose, sq.trans, sq.markers_sim, sq.errs, sq.iters, sq.status, E > 0 ? sq.shape : nullptr};
+            if (!dev && (rc = stage_in(fbs[q], NP, P, (E > 0 && sq.F >= 1) ? (size_t)sq.F * E : 0, stream, &bufs.st[q]))) return rc;
+            dbs[q] = dev ? fbs[q] : bufs.st[q].rows;
         }
+        if (E > 0) {   // extended variant: per-chain scratch for the shape derivatives of the joint transforms
+            qbytes = qscratch_bytes(cfg, m->K, E);
+            if ((rc = m->qscratch.reserve(qbytes * NC, stream))) return rc;
+        }
+        return MOSHII_OK;
     }
-    auto make_chain = [&](const Chunk& ck, int from, int idx, bool repair) {
-        // a chain over frames [from, ck.e) of its sequence; rows are addressed relative to `from`
+
+    // a chain over frames [from, ck.e) of its sequence; rows are addressed relative to `from`
+    ChainDev make_chain(const Chunk& ck, int from, int idx, bool repair) const {
         const FrameBufs& b = dbs[ck.seq];
         const size_t M = b.M;
         ChainDev cd;
@@ -1552,7 +1517,7 @@ int moshii_sequence_solve(moshii_model_t m, moshii_prior_t prior, const moshii_s
         cd.iters = b.iters ? b.iters + (size_t)from * 2 : nullptr;
         cd.status = b.status ? b.status + (size_t)from : nullptr;
         if (E > 0) {
-            cd.shape = shp[ck.seq] ? shp[ck.seq] + (size_t)from * E : nullptr;
+            cd.shape = b.shape ? b.shape + (size_t)from * E : nullptr;
             cd.qscratch = (double*)(m->qscratch.ptr + qbytes * idx);      // repair chains reuse the slot of their first chunk
         }
         cd.final_state = d_final + (size_t)idx * S;
@@ -1563,43 +1528,32 @@ int moshii_sequence_solve(moshii_model_t m, moshii_prior_t prior, const moshii_s
         if (repair) {
             cd.init_state = d_final + (size_t)ck.pred * S;
             cd.rejoin_tol = rejoin ? tol : 0.0;
-        } else if (ck.pred < 0 && d_init != nullptr && seqs[ck.seq].init_pose != nullptr) {
-            cd.init_state = d_init + (size_t)ck.seq * S;   // the sequence continues a chain instead of starting one
+        } else if (ck.pred < 0 && bufs.d_init != nullptr && seqs[ck.seq].init_pose != nullptr) {
+            cd.init_state = bufs.d_init + (size_t)ck.seq * S;   // the sequence continues a chain instead of starting one
         }
         return cd;
-    };
-    std::vector<ChainDev> cds(NC);
-    std::vector<int> pred(NC);
-    for (int c = 0; c < NC; ++c) { cds[c] = make_chain(chunks[c], chunks[c].a, c, false); pred[c] = chunks[c].pred; }
-    if (fuse)
-        for (int c = 0; c < NC; ++c) {
-            ChainDev& cd = cds[c];
-            cd.fuse_flags = d_fuse; cd.fuse_c = c; cd.fuse_count = d_fuse_count; cd.fuse_tol = tol;
-            cd.fuse_has_prev = (chunks[c].pred >= 0) ? 1 : 0;
-            const bool has_next = c + 1 < NC && chunks[c + 1].seq == chunks[c].seq;
-            if (!has_next) continue;
-            int cl = c + 1;   // one past the last chunk of the sequence
-            while (cl < NC && chunks[cl].seq == chunks[c].seq) ++cl;
-            // its own chunk as before, then -- if the hand-off to chunk c + 1 misses -- the repair chain that starts at chunk c + 1
-            cd.fuse_F = chunks[c].e - chunks[c].a;
-            cd.fuse_has_next = 1;
-            cd.F = chunks[cl - 1].e - chunks[c].a;
-            cd.final_state = d_final + (size_t)(cl - 1) * S;
-            cd.nb = cl - 1 - (c + 1);
-            cd.bnd = d_bnd + c + 2;
-            cd.bnd_off = chunks[c].a;
-            cd.run_final = d_final + (size_t)(c + 1) * S;
-            cd.run_entry = d_entry + (size_t)(c + 1) * S;
-            cd.baton = d_baton;
-            cd.abort_at = d_abort_at;
-            cd.chunk0 = c + 1;
-            cd.rejoin_tol = tol;
-        }
+    }
+
+    // ... which, its frame 0 being frame `from` of the sequence, re-solves chunk c0 and runs on through the following chunks to the end of the sequence
+    void run_through(ChainDev& cd, int c0, int from) const {
+        int cl = c0 + 1;   // one past the last chunk this chain may cover: the end of its sequence
+        while (cl < NC && chunks[cl].seq == chunks[c0].seq) ++cl;
+        cd.F = chunks[cl - 1].e - from;
+        cd.final_state = d_final + (size_t)(cl - 1) * S;
+        cd.nb = cl - 1 - c0;
+        cd.bnd = d_bnd + c0 + 1;
+        cd.bnd_off = from;
+        cd.run_final = d_final + (size_t)c0 * S;
+        cd.run_entry = d_entry + (size_t)c0 * S;
+        cd.baton = d_baton;
+        cd.abort_at = d_abort_at;
+        cd.chunk0 = c0;
+    }
+
     // The tail of pass 1 (ChainDev::tail_done): with cooperative repair sweeps the first launch's chains do not carry on, so the launch lasts as
     // long as its slowest chunk while the CUs of the others idle.  Once all but a fifth of a chip's worth of chains have ended, a chain with
     // more than a few frames to go gives its chunk up to the sweeps (which re-solve 16 frames in 2.5 ms).  MOSHII_TAIL_CUT=0 switches it off.
-    int n_tail_cut_armed = 0;
-    {
+    void arm_tail_cut(std::vector<ChainDev>& cds) const {
         static const int tail_env = []{ const char* e = getenv("MOSHII_TAIL_CUT"); return e ? atoi(e) : -1; }();
         const int spare = tail_env > 0 ? tail_env : std::max(8, n_cu / 5);     // (a tenth of the chip: 65.4 k frames/s on the bench's six sequences; a fifth: 65.9 k; none: 63.4 k)
         // Only where it pays: every chunk on a CU of its own from the start (one wave of workgroups: the order of finishing is the order of
@@ -1608,35 +1562,55 @@ int moshii_sequence_solve(moshii_model_t m, moshii_prior_t prior, const moshii_s
         // 2.5 ms of a cooperative sweep; the 195-frame chunks of a 50 000-frame sequence: 30 ms -- 372 -> 226 k frames/s when armed).
         int longest = 0;
         for (int c = 0; c < NC; ++c) longest = std::max(longest, chunks[c].e - chunks[c].s);
-        if (!fuse && coop_rep >= 2 && rejoin && tail_env != 0 && NC >= 4 * spare && NC <= n_cu && longest <= 32)
+        if (!(!fuse && coop_rep >= 2 && rejoin && tail_env != 0 && NC >= 4 * spare && NC <= n_cu && longest <= 32)) return;
+        for (int c = 0; c < NC; ++c) {
+            ChainDev& cd = cds[c];
+            cd.tail_done = d_fuse_count;                // (the carry-on counter: unused without the carry-on protocol, zeroed with the control words)
+            cd.tail_quota = NC - spare;
+            cd.tail_left = 3;
+            cd.tail_can_cut = chunks[c].pred >= 0 ? 1 : 0;
+            cd.tail_mark = d_abort_at + c;
+        }
+    }
+
+    // The pass-1 descriptors (plain; carrying on; giving up in the launch's tail) and the control words, then the first launch.
+    int launch_pass1() {
+        std::vector<ChainDev> cds(NC);
+        for (int c = 0; c < NC; ++c) cds[c] = make_chain(chunks[c], chunks[c].a, c, false);
+        if (fuse)
             for (int c = 0; c < NC; ++c) {
                 ChainDev& cd = cds[c];
-                cd.tail_done = d_fuse_count;                // (the carry-on counter: unused without the carry-on protocol, zeroed below)
-                cd.tail_quota = NC - spare;
-                cd.tail_left = 3;
-                cd.tail_can_cut = chunks[c].pred >= 0 ? 1 : 0;
-                cd.tail_mark = d_abort_at + c;
-                n_tail_cut_armed += cd.tail_can_cut;
+                cd.fuse_flags = d_fuse; cd.fuse_c = c; cd.fuse_count = d_fuse_count; cd.fuse_tol = tol;
+                cd.fuse_has_prev = (chunks[c].pred >= 0) ? 1 : 0;
+                const bool has_next = c + 1 < NC && chunks[c + 1].seq == chunks[c].seq;
+                if (!has_next) continue;
+                // its own chunk as before, then -- if the hand-off to chunk c + 1 misses -- the repair chain that starts at chunk c + 1
+                cd.fuse_F = chunks[c].e - chunks[c].a;
+                cd.fuse_has_next = 1;
+                run_through(cd, c + 1, chunks[c].a);
+                cd.rejoin_tol = tol;
             }
+        arm_tail_cut(cds);
+        HIP_TRY(hipMemcpyAsync(d_pass1, cds.data(), sizeof(ChainDev) * NC, hipMemcpyHostToDevice, stream));
+        {   // the control words behind the descriptors in ONE copy: [pred][chunk starts][done][baton x 2 = 0][abort_at = -1: no mark][fuse flags x 3, fuse count = 0]
+            std::vector<int> words((size_t)10 * NC + 1, 0);
+            for (int c = 0; c < NC; ++c) { words[c] = chunks[c].pred; words[(size_t)NC + c] = chunks[c].s; words[(size_t)5 * NC + c] = -1; }
+            HIP_TRY(hipMemcpyAsync(d_pred, words.data(), sizeof(int) * words.size(), hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipStreamSynchronize(stream));   // (`words` goes out of scope)
+        }
+        int rc = launch_chains(cfg, NC, d_pass1, stream);
+        if (rc) return rc;
+        hdev.assign(NC, 0.0);
+        if (fuse) {   // chains that carried on inside the first launch count as repairs (they did a repair chain's work)
+            HIP_TRY(hipMemcpyAsync(&n_repaired, d_fuse_count, sizeof(int), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (trace) fprintf(stderr, "[moshii] pass 1: %d chains carried on into the next chunk\n", n_repaired);
+        }
+        return MOSHII_OK;
     }
-    HIP_TRY(hipMemcpyAsync(d_pass1, cds.data(), sizeof(ChainDev) * NC, hipMemcpyHostToDevice, stream));
-    {   // the control words behind the descriptors in ONE copy: [pred][chunk starts][done][baton x 2 = 0][abort_at = -1: no mark][fuse flags x 3, fuse count = 0]
-        std::vector<int> words((size_t)10 * NC + 1, 0);
-        for (int c = 0; c < NC; ++c) { words[c] = pred[c]; words[(size_t)NC + c] = chunks[c].s; words[(size_t)5 * NC + c] = -1; }
-        HIP_TRY(hipMemcpyAsync(d_pred, words.data(), sizeof(int) * words.size(), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipStreamSynchronize(stream));   // (`words` goes out of scope)
-    }
-    if ((rc = launch_chains(cfg, NC, d_pass1, stream))) { cleanup(); return rc; }
-    // ---- verify the hand-offs; re-solve (exactly, from the predecessor's final state) the chunks that fail
-    std::vector<double> hdev(NC, 0.0);
-    int n_repaired = 0, rounds = 0;
-    if (fuse) {   // chains that carried on inside the first launch count as repairs (they did a repair chain's work)
-        HIP_TRY(hipMemcpyAsync(&n_repaired, d_fuse_count, sizeof(int), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (trace) fprintf(stderr, "[moshii] pass 1: %d chains carried on into the next chunk\n", n_repaired);
-    }
-    double max_dev = 0.0;
-    while (true) {
+
+    // hdev[c]: how far chunk c's entry state is from its predecessor's end state, or a verdict (k_verify_chunks)
+    int verify() {
         hipLaunchKernelGGL(k_verify_chunks, dim3(NC), dim3(64), 0, stream, NC, NP, E, d_pred, d_entry, d_final, d_dev);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(hdev.data(), d_dev, sizeof(double) * NC, hipMemcpyDeviceToHost, stream));
@@ -1647,117 +1621,56 @@ int moshii_sequence_solve(moshii_model_t m, moshii_prior_t prior, const moshii_s
                 fclose(fp);
             }
         }
-        std::vector<char> failing(NC, 0);
-        for (int c = 0; c < NC; ++c) failing[c] = chunks[c].pred >= 0 && !(hdev[c] <= tol);
         if (trace && NC <= 16) { fprintf(stderr, "[moshii] hand-off deviations:"); for (int c = 0; c < NC; ++c) fprintf(stderr, " %.1e", hdev[c]); fprintf(stderr, "\n"); }
-        for (int c = 0; c < NC; ++c)
-            if (chunks[c].pred >= 0 && hdev[c] >= 2e300) {   // NaN in a hand-off state: repairing cannot make it verify
-                cleanup_shape(); cleanup();
-                return fail(MOSHII_ERR_NUMERIC, "a chunk hand-off state is NaN");
-            }
-        if (rounds > NC + 1) {   // every round makes at least the first failing hand-off of a sequence exact: NC rounds is the worst case
-            cleanup_shape(); cleanup();
-            return fail(MOSHII_ERR_NUMERIC, "chunk hand-offs did not verify within the round limit");
+        return MOSHII_OK;
+    }
+
+    // a round of cooperative sweeps, g_round workgroups each: its launch configuration (prepared when first used) and exchange buffers
+    int prepare_coop_round(int g_round, const std::vector<int>& todo, std::vector<ChainDev>& rep) {
+        int rc;
+        LaunchCfg& cc = coop_cfgs[g_round];
+        if (cc.coop_g != g_round) {
+            size_t ctl2 = 0;
+            // (n_workgroups = 1: the residency of this round's chains has been settled by the caller)
+            if ((rc = prepare_launch(m, prior, o, Mmax, Nvmax, NWmax, 1, stream, extra, &cc, &ctl2, g_round))) return rc;
+            if (cc.coop_g != g_round) return fail(MOSHII_ERR_ARG, "internal: cooperative repair launch not prepared");
+            if (ctl2 != ctl) return fail(MOSHII_ERR_ARG, "internal: control block moved");
         }
-        // Scheduling of the repair chains (any mistake here only costs time: whatever ends up inconsistent fails the next
-        // verification).  A GROSS miss (> 1e-6) is a chunk whose fresh start sat in another basin: its repair chain may have
-        // to run through several chunks before it re-joins, so it owns everything up to the next gross miss.  A SLIGHT
-        // miss is a warm-up that had not quite converged: its chain re-joins within a few frames; slight misses that lie in
-        // a gross chain's span wait for the next round (they may be swept anyway), the others are repaired right away.
-        std::vector<int> todo;
-        std::vector<char> todo_gross;
-        {
-            const double gross_dev = 1e-6;
-            // ... except when the slight miss lies far (>= far_frames) behind the start of the gross chain whose span it is in:
-            // gross chains re-join within ~140 frames on every sequence looked at, so such a chunk is repaired right away and
-            // bounds that chain (should the chain ever get there, the next round continues it).
-            static const int far_frames = []{ const char* e = getenv("MOSHII_FAR_FRAMES"); return e ? atoi(e) : 160; }();
-            int seq = -1, span_start = 0;
-            bool in_span = false;
-            for (int c = 0; c < NC; ++c) {
-                if (chunks[c].seq != seq) { seq = chunks[c].seq; in_span = false; }
-                if (!failing[c]) continue;
-                const int p = chunks[c].pred;
-                // Chunks a pass-1 chain gave up in the launch's tail (5e299: ChainDev::tail_done) are re-solved like gross misses -- they
-                // are the hard stretches, their sweeps run 30-70 frames -- but neither they nor their successors (4e299: the entry state
-                // stands against a spoiled end state; the sweep hands over at the boundary) say anything about the chunks behind them:
-                // as predecessors they do not hold back a gross miss's chain (they did: a cascade of one round per territory).
-                const bool aftercut = hdev[c] == 4e299, p_given_up = failing[p] && hdev[p] >= 1e299 && hdev[p] < 1e300;
-                const bool g = rejoin && hdev[c] > gross_dev, pg = rejoin && failing[p] && hdev[p] > gross_dev && !p_given_up;
-                if (rejoin && aftercut) continue;
-                if (!rejoin) { if (!failing[p]) { todo.push_back(c); todo_gross.push_back(0); } continue; }
-                if (g) { if (!pg) { todo.push_back(c); todo_gross.push_back(1); in_span = true; span_start = chunks[c].s; } }
-                else if (!in_span || (far_frames > 0 && chunks[c].s - span_start >= far_frames && !failing[p])) { todo.push_back(c); todo_gross.push_back(0); }
-            }
-        }
-        if (todo.empty()) break;
-        // Every repair chain starts at its failing chunk and runs on through the following chunks of its sequence until it
-        // re-joins the stored trajectory.  Where it reaches the start of another chain of this round, it takes over from it
-        // (ChainDev::baton): a cascade of adjacent wrong regions is swept by ONE chain in one round, while regions that turn
-        // out to be independent are still repaired side by side.  (Before the baton each chain ended at the next chain's
-        // start: a cascade cost one round per region, each as long as the longest chain of that round.)
+        if ((rc = reserve_exchange(m, cc.coop, rep.size(), stream))) return rc;
+        for (size_t i = 0; i < rep.size(); ++i)
+            fill_coop(rep[i], cc, seqs[chunks[todo[i]].seq].attach->M, m->coopbuf.ptr + cc.coop.bytes_per_chain * i);
+        return MOSHII_OK;
+    }
+
+    // Re-solves (exactly, from the predecessor's final state) the chunks of `todo` in one launch.
+    // Every repair chain starts at its failing chunk and runs on through the following chunks of its sequence until it
+    // re-joins the stored trajectory.  Where it reaches the start of another chain of this round, it takes over from it
+    // (ChainDev::baton): a cascade of adjacent wrong regions is swept by ONE chain in one round, while regions that turn
+    // out to be independent are still repaired side by side.  (Before the baton each chain ended at the next chain's
+    // start: a cascade cost one round per region, each as long as the longest chain of that round.)
+    int repair_round(const std::vector<int>& todo) {
+        int rc;
         std::vector<ChainDev> rep(todo.size());
         std::vector<int> hbaton(2 * (size_t)NC, 0);
-        for (size_t i = 0; i < todo.size(); ++i) hbaton[2 * (size_t)todo[i]] = 1;
         for (size_t i = 0; i < todo.size(); ++i) {
             const int c = todo[i];
-            int cl = c + 1;   // one past the last chunk this chain may cover: the end of its sequence
-            while (cl < NC && chunks[cl].seq == chunks[c].seq) ++cl;
-            ChainDev cd = make_chain(chunks[c], chunks[c].s, c, true);
-            cd.F = chunks[cl - 1].e - chunks[c].s;
-            cd.final_state = d_final + (size_t)(cl - 1) * S;
-            cd.nb = cl - 1 - c;
-            cd.bnd = d_bnd + c + 1;
-            cd.bnd_off = chunks[c].s;
-            cd.run_final = d_final + (size_t)c * S;
-            cd.run_entry = d_entry + (size_t)c * S;
-            cd.baton = d_baton;
-            cd.abort_at = d_abort_at;
-            cd.chunk0 = c;
+            hbaton[2 * (size_t)c] = 1;
+            ChainDev& cd = rep[i] = make_chain(chunks[c], chunks[c].s, c, true);
+            run_through(cd, c, chunks[c].s);
             if (!rejoin) { cd.F = chunks[c].e - chunks[c].s; cd.nb = 0; cd.final_state = d_final + (size_t)c * S; cd.baton = nullptr; cd.abort_at = nullptr; }   // (one chunk per chain)
             cd.frames_done = trace ? d_done + i : nullptr;
-            rep[i] = cd;
         }
         // cooperative sweeps: as many workgroups per chain as the request and the chip allow (every workgroup of the launch resident)
-        int g_round = 0;
-        if (coop_rep >= 2) g_round = std::min(coop_rep, n_cu / (int)rep.size());
-        const LaunchCfg* use = &cfg;
-        if (g_round >= 2) {
-            LaunchCfg& cc = coop_cfgs[g_round];
-            if (!coop_cfg_ready[g_round]) {
-                size_t ctl2 = 0;
-                // (n_workgroups = 1: the residency of this round's chains has been settled just above)
-                if ((rc = prepare_launch(m, prior, o, Mmax, Nvmax, NWmax, 1, stream, extra, &cc, &ctl2, g_round))) { cleanup(); return rc; }
-                if (cc.coop_g != g_round) { cleanup(); return fail(MOSHII_ERR_ARG, "internal: cooperative repair launch not prepared"); }
-                if (ctl2 != ctl) { cleanup(); return fail(MOSHII_ERR_ARG, "internal: control block moved"); }
-                coop_cfg_ready[g_round] = 1;
-            }
-            const size_t per = ((size_t)2 * g_round * cc.coop_slot_doubles * sizeof(unsigned long long) + (size_t)(2 * g_round + 2) * sizeof(unsigned) + 255) & ~size_t(255);
-            if ((rc = m->coopbuf.reserve(per * rep.size()))) { cleanup(); return rc; }
-            m->coopbuf.used = true; m->coopbuf.last_stream = stream;
-            HIP_TRY(hipMemsetAsync(m->coopbuf.ptr, 0, per * rep.size(), stream));
-            for (size_t i = 0; i < rep.size(); ++i) {
-                ChainDev& cd = rep[i];
-                cd.coop.G = g_round; cd.coop.prior_rank = cc.coop_prior_rank; cd.coop.slot_doubles = cc.coop_slot_doubles; cd.coop.skew = coop_skew_env();
-                    coop_split(seqs[chunks[todo[i]].seq].attach->M, g_round, cc.coop_prior_frac, cd.coop.mlo);
-                char* cb = m->coopbuf.ptr + per * i;
-                cd.coop.slots = as_gp_rw((unsigned long long*)cb);
-                cd.coop.flags = as_gp_rw((unsigned*)(cb + (size_t)2 * g_round * cc.coop_slot_doubles * sizeof(unsigned long long)));
-            }
-            use = &cc;
-        }
+        const int g_round = (coop_rep >= 2) ? std::min(coop_rep, n_cu / (int)rep.size()) : 0;
+        if (g_round >= 2 && (rc = prepare_coop_round(g_round, todo, rep))) return rc;
+        const LaunchCfg& use = (g_round >= 2) ? coop_cfgs[g_round] : cfg;
         HIP_TRY(hipMemcpyAsync(d_baton, hbaton.data(), sizeof(int) * hbaton.size(), hipMemcpyHostToDevice, stream));
         HIP_TRY(hipMemcpyAsync(d_repair, rep.data(), sizeof(ChainDev) * rep.size(), hipMemcpyHostToDevice, stream));
         HIP_TRY(hipStreamSynchronize(stream));
-        if ((rc = launch_chains(*use, (int)rep.size(), d_repair, stream))) { cleanup(); return rc; }
-        if (g_round >= 2) {   // did every group stay whole?
-            const size_t per = ((size_t)2 * g_round * use->coop_slot_doubles * sizeof(unsigned long long) + (size_t)(2 * g_round + 2) * sizeof(unsigned) + 255) & ~size_t(255);
-            std::vector<unsigned> ab(rep.size(), 0u);   // (one strided copy: a copy per chain was 22 us a chain, 0.5-1 ms a round)
-            HIP_TRY(hipMemcpy2DAsync(ab.data(), sizeof(unsigned), m->coopbuf.ptr + (size_t)2 * g_round * use->coop_slot_doubles * sizeof(unsigned long long) + g_round * sizeof(unsigned),
-                                     per, sizeof(unsigned), rep.size(), hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
+        if ((rc = launch_chains(use, (int)rep.size(), d_repair, stream))) return rc;
+        if (g_round >= 2) {
             bool broken = false;
-            for (size_t i = 0; i < rep.size(); ++i) broken |= ab[i] != 0u;
+            if ((rc = coop_any_broken(m, use.coop, rep.size(), stream, &broken))) return rc;
             if (broken) {   // (the chip is shared?)  Whatever the broken groups left is caught by the next verification -- they spoil the entry state of
                             // the chunk they stopped in -- and re-solved by plain chains from here on
                 note_coop_broken("moshii_sequence_solve");
@@ -1774,21 +1687,65 @@ int moshii_sequence_solve(moshii_model_t m, moshii_prior_t prior, const moshii_s
             for (size_t i = 0; i < rep.size(); ++i) fprintf(stderr, " %d:%.0e:%d/%d", todo[i], hdev[todo[i]], done[i], rep[i].F);
             fprintf(stderr, "\n");
         }
+        return MOSHII_OK;
     }
-    for (int c = 0; c < NC; ++c) if (chunks[c].pred >= 0) max_dev = std::max(max_dev, hdev[c]);
-    if (report) { report->n_chunks = NC; report->n_repaired = n_repaired; report->repair_rounds = rounds; report->max_handoff_dev = max_dev;
-                  report->warmup = warmup; report->verify_tol = tol; }
-    if (!dev)
+
+    int finish(moshii_chunk_report* report) {
+        double max_dev = 0.0;
+        for (int c = 0; c < NC; ++c) if (chunks[c].pred >= 0) max_dev = std::max(max_dev, hdev[c]);
+        if (report) { report->n_chunks = NC; report->n_repaired = n_repaired; report->repair_rounds = rounds; report->max_handoff_dev = max_dev;
+                      report->warmup = warmup; report->verify_tol = tol; }
+        if (dev) return MOSHII_OK;
+        int rc;
+        HIP_TRY(hipStreamSynchronize(stream));
         for (int q = 0; q < n_seq; ++q)
-            if ((rc = stage_out(fbs[q], NP, P, &st[q]))) { cleanup_shape(); cleanup(); return rc; }
-    if (!dev && E > 0) {
-        hipStreamSynchronize(stream);
-        for (int q = 0; q < n_seq; ++q)
-            if (shp[q] && seqs[q].shape) hipMemcpy(seqs[q].shape, shp[q], (size_t)seqs[q].F * E * sizeof(double), hipMemcpyDeviceToHost);
+            if ((rc = stage_out(fbs[q], NP, P, E, bufs.st[q]))) return rc;
+        return MOSHII_OK;
     }
-    cleanup_shape();
-    cleanup();
-    return MOSHII_OK;
+};
+
+}  // namespace
+
+extern "C" {
+
+int moshii_chain_solve(moshii_model_t m, moshii_prior_t prior, const moshii_solve_opts* o, int32_t n_chains,
+                       const moshii_chain_desc* chains, uint32_t flags, void* stream_) {
+    if (!m || !o || !chains || n_chains < 1) return fail(MOSHII_ERR_ARG, "bad argument");
+    bool broken = false;
+    int rc = chain_solve_once(m, prior, o, n_chains, chains, flags, (hipStream_t)stream_, &broken);
+    if (rc || !broken) return rc;
+    // the same solve as plain chains, over whatever the broken groups left in the rows (the first attempt's buffers are gone by now)
+    note_coop_broken("moshii_chain_solve");
+    return chain_solve_once(m, prior, o, n_chains, chains, (flags & ~0xff00u) | (1u << 8), (hipStream_t)stream_, &broken);
+}
+
+int moshii_plan_chunks(int32_t F, int32_t num_chunks, int32_t warmup, int32_t cap, int32_t* starts, int32_t* launch_starts) {
+    if (F < 0 || num_chunks < 1 || warmup < 0 || cap < 1 || !starts || !launch_starts) return fail(MOSHII_ERR_ARG, "bad argument");
+    return solve_plan::plan_chunks(F, num_chunks, warmup, cap, starts, launch_starts);
+}
+
+int moshii_sequence_solve(moshii_model_t m, moshii_prior_t prior, const moshii_solve_opts* o, int32_t n_seq,
+                          const moshii_sequence_desc* seqs, const moshii_chunk_opts* co, uint32_t flags, void* stream_,
+                          moshii_chunk_report* report) {
+    if (!m || !o || !seqs || n_seq < 1) return fail(MOSHII_ERR_ARG, "bad argument");
+    SeqSolve s{m, prior, o, n_seq, seqs, co, flags, (hipStream_t)stream_};
+    if (s.E > 0 && s.E != m->nshape) return fail(MOSHII_ERR_ARG, "n_shape does not match moshii_model_set_free_shape");
+    int rc;
+    if ((rc = s.plan()) || (rc = s.prepare()) || (rc = s.stage()) || (rc = s.launch_pass1())) return rc;
+    // ---- verify the hand-offs; re-solve the chunks that fail, round by round
+    while (true) {
+        if ((rc = s.verify())) return rc;
+        for (int c = 0; c < s.NC; ++c)
+            if (s.chunks[c].pred >= 0 && s.hdev[c] >= MOSHII_HANDOFF_NAN)   // repairing cannot make it verify
+                return fail(MOSHII_ERR_NUMERIC, "a chunk hand-off state is NaN");
+        if (s.rounds > s.NC + 1)   // every round makes at least the first failing hand-off of a sequence exact: NC rounds is the worst case
+            return fail(MOSHII_ERR_NUMERIC, "chunk hand-offs did not verify within the round limit");
+        static const int far_frames = []{ const char* e = getenv("MOSHII_FAR_FRAMES"); return e ? atoi(e) : 160; }();
+        const solve_plan::Repairs rep = solve_plan::pick_repairs(s.chunks, s.hdev, s.tol, s.rejoin, far_frames);
+        if (rep.todo.empty()) break;
+        if ((rc = s.repair_round(rep.todo))) return rc;
+    }
+    return s.finish(report);
 }
 
 int moshii_stagei_solve(moshii_model_t m, moshii_prior_t prior, const moshii_stagei_desc* desc, void* stream) {

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "solve_plan.h"   // MOSHII_HANDOFF_* / MOSHII_MARK_*: the hand-off verdicts and marks the kernels share with the host scheduler
 
 #define MOSHII_MAXK 64      // joints (ancestor sets are 64-bit masks)
 

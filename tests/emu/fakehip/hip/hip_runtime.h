@@ -60,8 +60,16 @@ enum { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorUnknown = 999 };
 enum hipMemcpyKind { hipMemcpyHostToHost, hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice, hipMemcpyDefault };
 enum { hipDeviceAttributeMultiprocessorCount = 1, hipFuncAttributeMaxDynamicSharedMemorySize = 2 };
 
-template <class T> inline hipError_t hipMalloc(T** p, size_t n) { *p = (T*)calloc(1, n ? n : 1); return *p ? hipSuccess : hipErrorUnknown; }
-inline hipError_t hipFree(void* p) { free(p); return hipSuccess; }
+// (test aid, hip_emu_runtime.cpp: allocations made / still live, and a countdown after which ONE hipMalloc fails -- error paths must free what the call allocated)
+namespace hipemu { extern long malloc_calls, live_allocs, fail_malloc_in; }
+template <class T> inline hipError_t hipMalloc(T** p, size_t n) {
+    ++hipemu::malloc_calls;
+    if (hipemu::fail_malloc_in > 0 && --hipemu::fail_malloc_in == 0) { *p = nullptr; return hipErrorUnknown; }
+    *p = (T*)calloc(1, n ? n : 1);
+    if (*p) ++hipemu::live_allocs;
+    return *p ? hipSuccess : hipErrorUnknown;
+}
+inline hipError_t hipFree(void* p) { if (p) --hipemu::live_allocs; free(p); return hipSuccess; }
 inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { if (n) memcpy(d, s, n); return hipSuccess; }
 inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { if (n) memcpy(d, s, n); return hipSuccess; }
 inline hipError_t hipMemcpy2DAsync(void* d, size_t dpitch, const void* s, size_t spitch, size_t width, size_t height, hipMemcpyKind, hipStream_t) {

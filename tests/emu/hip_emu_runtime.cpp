@@ -223,5 +223,9 @@ void launch(dim3 grid, dim3 block, size_t lds_bytes, const std::function<void()>
     cur_fiber = -1;
     if (profiling) { ProfRow& r = prof()[name_now]; r.s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_launch0).count(); r.n += 1; r.fibers += (long)grid.x * grid.y * grid.z * nt; }
 }
+long malloc_calls = 0, live_allocs = 0, fail_malloc_in = 0;
 }  // namespace hipemu
 void hipemu_yield() { sched_yield(); }
+extern "C" long hipemu_malloc_calls() { return hipemu::malloc_calls; }
+extern "C" long hipemu_live_allocs() { return hipemu::live_allocs; }
+extern "C" void hipemu_fail_malloc_in(long n) { hipemu::fail_malloc_in = n; }   // the n-th hipMalloc from now fails (0: none)

@@ -334,3 +334,43 @@ def test_extended_kernel_with_more_than_127_unknowns_in_emulation(monkeypatch, E
     np.testing.assert_array_equal(out['iters'][:, 0], ref['iters'])
     assert np.all(out['status'] == 0)
 
+
+
+@pytest.mark.parametrize('entry', ['chain', 'sequence'])
+def test_a_failed_allocation_frees_what_the_call_allocated_in_emulation(entry):
+    """moshii_chain_solve / moshii_sequence_solve on host buffers stage nine device arrays per chain or sequence.  When one of those
+    allocations fails -- the first, a middle one, the last (the stand-in runtime counts hipMalloc calls and fails the n-th on request)
+    -- the call reports MOSHII_ERR_HIP, leaves no allocation behind, and the next call solves as if nothing had happened."""
+    case = oracle_case('smplh', F=8, M=53, seed=7)
+    with emulated_libmoshii() as capi:
+        import ctypes as C
+        lib = capi.load()
+        lib.hipemu_malloc_calls.restype = lib.hipemu_live_allocs.restype = C.c_long
+        lib.hipemu_fail_malloc_in.argtypes = [C.c_long]
+        dev = device_case(case)
+        args = (dev['model'], dev['prior'], dev['opts'])
+
+        def solve():
+            if entry == 'chain':
+                return capi.chain_solve_host(*args, [dict(attach=dev['attach'], obs=case['obs'], vis=case['vis'], first=True)])[0]
+            return capi.sequence_solve_host(*args, [dict(attach=dev['attach'], obs=case['obs'], vis=case['vis'])],
+                                            num_chunks=2, warmup=3, verify_tol=1e-9)[0][0]
+
+        def same(a, b):
+            return all(np.array_equal(a[k], b[k]) for k in a)
+
+        first = solve()                                  # (the buffers kept with the model have their size from here on)
+        before = lib.hipemu_malloc_calls()
+        assert same(solve(), first)
+        n = lib.hipemu_malloc_calls() - before           # hipMalloc calls of one call
+        assert n >= 9
+        for nth in (1, (n + 1) // 2, n):
+            live = lib.hipemu_live_allocs()
+            lib.hipemu_fail_malloc_in(nth)
+            try:
+                with pytest.raises(capi.MoshiiError, match=r'libmoshii error -2:'):   # MOSHII_ERR_HIP
+                    solve()
+            finally:
+                lib.hipemu_fail_malloc_in(0)
+            assert lib.hipemu_live_allocs() == live, (nth, n)
+            assert same(solve(), first), nth

@@ -2005,6 +2005,10 @@ __device__ void assemble(const Ctx& cx, const ChainLayout& ly, const ModelDev& m
     for (int e = tid; e < 3 * Tm * LDJ; e += MOSHII_TPB) cx.Jrow[e] = 0.0;
     // Jacobian-only joint quantities at the current point (the forward state of the last evaluation is in LDS):
     // left-Jacobian columns a_c of each joint rotation and dR/dtheta_c = [a_c]x R
+    // The per-joint chain (a_c, dR/dtheta_c, then omega from a_c) belongs to wavefront 0 alone, whose LDS operations complete in order: no
+    // workgroup barrier inside it.  It shares nothing with T0 of the first tile, which wavefronts 1..3 run meanwhile (lanes 64.. below);
+    // the barrier that ends T0 publishes both to T1.
+    if (tid < 64) {
     if (tid < md.K) {
         double R[9], Jl[9];
         rodrigues_dev(&cx.fullpose[3 * tid], R, Jl);
@@ -2023,15 +2027,17 @@ __device__ void assemble(const Ctx& cx, const ChainLayout& ly, const ModelDev& m
             }
         }
     }
-    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
     // world rotation axes omega_{k,c} = Rw_par(k) . a_{k,c}   (published by the barrier that ends T0)
-    if (tid < 3 * md.K) {
-        const int k = tid / 3, c = tid % 3;
+    for (int i = tid; i < 3 * md.K; i += 64) {
+        const int k = i / 3, c = i % 3;
         const double ax = cx.acol[k * 9 + c * 3 + 0], ay = cx.acol[k * 9 + c * 3 + 1], az = cx.acol[k * 9 + c * 3 + 2];
         double ox = ax, oy = ay, oz = az;
         if (k > 0) mat3_vec(&cx.Rw[md.parents[k] * 9], ax, ay, az, ox, oy, oz);
         cx.omega[k * 10 + c * 3 + 0] = ox; cx.omega[k * 10 + c * 3 + 1] = oy; cx.omega[k * 10 + c * 3 + 2] = oz;
     }
+    }   // (wavefront 0)
     }   // (rows_here)
     if constexpr (XT) {
         if (nshp > 0 && rows_here) {
@@ -2072,13 +2078,17 @@ __device__ void assemble(const Ctx& cx, const ChainLayout& ly, const ModelDev& m
         }
     }
     const int v_lo = COOP ? fp.v0 : 0, v_hi = COOP ? fp.v1 : fp.nobs;
+    if (v_hi <= v_lo) __syncthreads();   // (uniform; no tile: nothing else ends the prologue above)
     for (int tile0 = v_lo; tile0 < v_hi; tile0 += Tm) {
         const int cnt = min(Tm, v_hi - tile0);
         const int ntv = 3 * cnt;
         // T0: per tile vertex blended rotation + rigidly-attached positions; per tile marker local Jacobian
-        if (tid < ntv) {
-            const int m = cx.visidx[tile0 + tid / 3];
-            const int av = 3 * m + tid % 3;
+        // (tile vertices on lanes 64 .. 64 + 3 cnt, tile markers on lanes 192 .. 192 + cnt, 3 Tm <= 120: wavefront 0 is busy with the per-joint chain
+        //  during the first tile's T0)
+        const int tl = tid - 64;
+        if (tl >= 0 && tl < ntv) {
+            const int m = cx.visidx[tile0 + tl / 3];
+            const int av = 3 * m + tl % 3;
             const double px = cx.vposed[av * 3 + 0], py = cx.vposed[av * 3 + 1], pz = cx.vposed[av * 3 + 2];
             double Tr[9];
 #pragma unroll
@@ -2086,11 +2096,11 @@ __device__ void assemble(const Ctx& cx, const ChainLayout& ly, const ModelDev& m
             auto influence = [&](int s, int j, double w) {
                 double ox, oy, oz;
                 mat3_vec(&cx.Rw[j * 9], px - cx.Jl[j * 3 + 0], py - cx.Jl[j * 3 + 1], pz - cx.Jl[j * 3 + 2], ox, oy, oz);
-                cx.xjs[tid * XS + s * 4 + 0] = ox + cx.tw[j * 3 + 0];
-                cx.xjs[tid * XS + s * 4 + 1] = oy + cx.tw[j * 3 + 1];
-                cx.xjs[tid * XS + s * 4 + 2] = oz + cx.tw[j * 3 + 2];
-                cx.xjs[tid * XS + s * 4 + 3] = w;
-                cx.tjs[tid * TS + s] = j;
+                cx.xjs[tl * XS + s * 4 + 0] = ox + cx.tw[j * 3 + 0];
+                cx.xjs[tl * XS + s * 4 + 1] = oy + cx.tw[j * 3 + 1];
+                cx.xjs[tl * XS + s * 4 + 2] = oz + cx.tw[j * 3 + 2];
+                cx.xjs[tl * XS + s * 4 + 3] = w;
+                cx.tjs[tl * TS + s] = j;
 #pragma unroll
                 for (int e = 0; e < 9; ++e) Tr[e] += w * cx.Rw[j * 9 + e];
             };
@@ -2105,9 +2115,9 @@ __device__ void assemble(const Ctx& cx, const ChainLayout& ly, const ModelDev& m
                 for (int s = 0; s < NW; ++s) influence(s, gptr(at.wj)[av * NW + s], gptr(at.ww)[av * NW + s]);
             }
 #pragma unroll
-            for (int e = 0; e < 9; ++e) cx.Trot[tid * 10 + e] = Tr[e];
-        } else if (tid >= 128 && tid < 128 + cnt) {
-            const int ml = tid - 128;
+            for (int e = 0; e < 9; ++e) cx.Trot[tl * 10 + e] = Tr[e];
+        } else if (tid >= 192 && tid < 192 + cnt) {
+            const int ml = tid - 192;
             const int m = cx.visidx[tile0 + ml];
             const double c[3] = {gptr(at.coef)[m * 3 + 0], gptr(at.coef)[m * 3 + 1], gptr(at.coef)[m * 3 + 2]};
             double mk[3], L[27];
@@ -2118,11 +2128,16 @@ __device__ void assemble(const Ctx& cx, const ChainLayout& ly, const ModelDev& m
                 for (int row = 0; row < 3; ++row)
 #pragma unroll
                     for (int x = 0; x < 3; ++x) cx.Lm[(ml * 3 + sv) * 10 + row * 3 + x] = L[row * 9 + sv * 3 + x];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) cx.Jrow[(3 * ml + i) * LDJ + n] = cx.res[m * 3 + i];   // residual = column n of the tile (T3)
         }
         __syncthreads();
         PROF_LAP(4);
+        // residual = column n of the tile (T3).  Behind the barrier: the first tile's T0 runs beside the zeroing of the tile above.
+        if (tid >= 192 && tid < 192 + cnt) {
+            const int ml = tid - 192;
+            const int m = cx.visidx[tile0 + ml];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) cx.Jrow[(3 * ml + i) * LDJ + n] = cx.res[m * 3 + i];
+        }
         // T1: marker rows, fused over the marker's three vertices: item = (tile marker, needed joint), marker fastest so
         // that the posedirs gathers of a wavefront fall into a few contiguous runs.  For each vertex
         //   dv/dtheta_{k,c} = omega_{k,c} x sum_{j in subtree(k)} w_j (x_j - t_k)  +  Trot . (P_k . vec([a_c]x R_k))
@@ -2314,9 +2329,15 @@ __device__ void assemble(const Ctx& cx, const ChainLayout& ly, const ModelDev& m
         auto exchange = [&](auto l2) {   // (l2: the access scope, see coop_st_l2)
             constexpr bool L2 = decltype(l2)::value;
             const CoopSlot mine = coop_slot16(co, seq, co.rank);
+            constexpr bool RS = NT >= 9;   // reduce-scatter + all-gather instead of the all-gather of every rank's whole slot (below)
+            // All-gather form: a prior rank without markers has built no rows -- its accumulators are the +0.0 of acc.zero().  It posts its
+            // NUP prior units only and nobody loads its accumulator units.  Every sum below starts from +0.0 and is taken in rank order, and a
+            // sum that starts from +0.0 is never -0.0 (x + -x rounds to +0.0, +0.0 + -0.0 is +0.0), so leaving a +0.0 addend out moves no bit.
+            const bool bare_prior = !RS && co.prior_bare != 0;   // (uniform, the same on every rank)
+            const bool post_acc = !(bare_prior && co.rank == co.prior_rank);
 #pragma unroll
             for (int t = 0; t < NT; ++t)
-                if (4 * t + wv < NE) {   // (uniform: the tile slots beyond the last tile hold zeros nobody reads)
+                if (post_acc && 4 * t + wv < NE) {   // (uniform: the tile slots beyond the last tile hold zeros nobody reads)
                     coop_st16<L2>(mine, (2 * t) * MOSHII_TPB + tid, acc.c[t][0], acc.c[t][1]);
                     coop_st16<L2>(mine, (2 * t + 1) * MOSHII_TPB + tid, acc.c[t][2], acc.c[t][3]);
                 }
@@ -2355,7 +2376,6 @@ __device__ void assemble(const Ctx& cx, const ChainLayout& ly, const ModelDev& m
 #pragma unroll
                 for (int u = 0; u < NUP; ++u) coop_st16<L2>(mine, (NUA + u) * MOSHII_TPB + tid, pe[2 * u], pe[2 * u + 1]);
             }
-            constexpr bool RS = NT >= 9;   // reduce-scatter + all-gather instead of the all-gather of every rank's whole slot (below)
             double own[RS ? 1 : 4 * NT];
             if constexpr (!RS) {
 #pragma unroll
@@ -2414,25 +2434,35 @@ __device__ void assemble(const Ctx& cx, const ChainLayout& ly, const ModelDev& m
                 }
                 for (int r0 = 0; r0 < co.G; r0 += RB) {
                     double v[RB][4 * NT];
+                    // (no loads for the own slot -- its values are in `own` -- nor for a marker-less prior rank's, see bare_prior above)
+                    auto wanted = [&](int r) { return r < co.G && r != co.rank && !(bare_prior && r == co.prior_rank); };   // (uniform)
 #pragma unroll
                     for (int u = 0; u < RB; ++u) {
-                        const CoopSlot sr = coop_slot16(co, seq, min(r0 + u, co.G - 1));
+                        if (wanted(r0 + u)) {
+                            const CoopSlot sr = coop_slot16(co, seq, r0 + u);
 #pragma unroll
-                        for (int t = 0; t < NT; ++t)
-                            if (4 * t + wv < NE) {
-                                coop_ld16<L2>(sr, (2 * t) * MOSHII_TPB + tid, v[u][4 * t], v[u][4 * t + 1]);
-                                coop_ld16<L2>(sr, (2 * t + 1) * MOSHII_TPB + tid, v[u][4 * t + 2], v[u][4 * t + 3]);
-                            }
+                            for (int t = 0; t < NT; ++t)
+                                if (4 * t + wv < NE) {
+                                    coop_ld16<L2>(sr, (2 * t) * MOSHII_TPB + tid, v[u][4 * t], v[u][4 * t + 1]);
+                                    coop_ld16<L2>(sr, (2 * t + 1) * MOSHII_TPB + tid, v[u][4 * t + 2], v[u][4 * t + 3]);
+                                }
+                        }
                     }
 #pragma unroll
                     for (int u = 0; u < RB; ++u) {
-                        if (r0 + u < co.G) {   // (uniform)
-                            const bool mine_ = (r0 + u) == co.rank;
+                        if ((r0 + u) == co.rank) {   // (uniform)
 #pragma unroll
                             for (int t = 0; t < NT; ++t)
                                 if (4 * t + wv < NE) {
 #pragma unroll
-                                    for (int i = 0; i < 4; ++i) acc.c[t][i] += mine_ ? own[4 * t + i] : v[u][4 * t + i];
+                                    for (int i = 0; i < 4; ++i) acc.c[t][i] += own[4 * t + i];
+                                }
+                        } else if (wanted(r0 + u)) {
+#pragma unroll
+                            for (int t = 0; t < NT; ++t)
+                                if (4 * t + wv < NE) {
+#pragma unroll
+                                    for (int i = 0; i < 4; ++i) acc.c[t][i] += v[u][4 * t + i];
                                 }
                         }
                     }
@@ -3055,6 +3085,7 @@ __global__ __launch_bounds__(MOSHII_TPB, MINW) void k_chain_solve(const ChainDev
         const ChainDev* c0 = chains + chain_id;
         co.G = G; co.rank = q % G; co.prior_rank = c0->coop.prior_rank;
         co.mlo = c0->coop.mlo[co.rank]; co.mhi = c0->coop.mlo[co.rank + 1];
+        co.prior_bare = c0->coop.mlo[co.prior_rank + 1] == c0->coop.mlo[co.prior_rank];
         co.slot_doubles = c0->coop.slot_doubles; co.slots = c0->coop.slots; co.flags = c0->coop.flags; co.skew = c0->coop.skew;
     }
     const bool lead = !COOP || co.rank == 0;   // writes the rows every rank holds alike

@@ -109,6 +109,7 @@ struct CoopDev {
 // the rank's view, in KernelCtx
 struct CoopCtx {
     int G, rank, prior_rank, mlo, mhi, slot_doubles, skew;
+    int prior_bare;      // the prior rank owns no markers: its J^T J accumulators are zeros that it neither posts nor anybody loads (assemble())
     MOSHII_GP(unsigned long long) slots;
     MOSHII_GP(unsigned int) flags;
 };

@@ -74,7 +74,8 @@ const char* moshii_last_error(void);
  * caller built against the 100 header must not call a 101 library's moshii_stagei_solve (it would read past the caller's struct);
  * check moshii_version() >= 101 before filling a moshii_stagei_desc declared from this header, and zero the struct first.
  * 102: moshii_solve_opts grew by the joint-angle term.  103: moshii_lbs_forward_shape_*.  104: moshii_model_set_faces,
- * moshii_vertex_normals_*, moshii_virtual_markers_* (new calls only: no struct changed). */
+ * moshii_vertex_normals_*, moshii_virtual_markers_* (new calls only: no struct changed).  105: moshii_surface_distance_*,
+ * moshii_marker_surface_distance_* (new calls only). */
 int  moshii_version(void);
 /* first 16 hex digits of the SHA-256 over the sources this binary was compiled from (python -m moshpp_amd.build computes the same
  * over the tree: a stale binary is detectable); "unknown" for a build outside build.py */
@@ -191,7 +192,44 @@ int moshii_virtual_markers_f64(moshii_model_t m, int32_t F, const double* pose, 
                                uint32_t flags, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Pose prior.  Replaces create_gmm_body_prior / MaxMixtureComplete
+ * Signed point-to-mesh distance (version 105): how far from the skin every point sits, on every frame, and on which side.
+ * ------------------------------------------------------------------------------------------- */
+
+/* For every frame f and point i: the signed distance of points[f][i] to the mesh verts[f] with the handle's triangles -- the
+ * reference's PtsToMesh(signed=True) (scan2mesh/mesh_distance_main.py:158-297): exhaustive over all triangles, closest point by the
+ * region tests of the nearest-point query, ties to the lowest face id; sign of (p - nearest) . n with n the face normal (interior), the
+ * vertex normal (vertex) or the sum of the two vertex normals (edge), vertex normals as moshii_vertex_normals_* gives them (a zero sum:
+ * sign 0); dist = sqrt(d^2) * sign, positive outside.
+ *   dist[F][N]        metres
+ *   face[F][N]        the nearest face's id                                                      (or NULL)
+ *   part[F][N]        0 interior, 1 - 3 the edges ab / bc / ca, 4 - 6 the vertices a / b / c     (or NULL)
+ *   nearest[F][N][3]  the nearest point                                                          (or NULL)
+ * A point with a non-finite coordinate is absent: dist NaN, face -1, part -1, nearest NaN, and it costs no search.  A face that names
+ * a vertex twice never wins.
+ * _f32 searches in f32 and evaluates the winning triangle once in f64 from the f32 inputs, rounded on the store.  The search reads the
+ * vertices through L2; MOSHII_SD_KERNEL=lds in the environment takes, for _f32 frames within the LDS budget, the kernel in which a
+ * workgroup stages whole frames in LDS -- same bits, measured slower.  Buffers host or device per flags; asynchronous on `stream` with
+ * MOSHII_BUFFERS_DEVICE.  64-bit addressing throughout.  Before moshii_model_set_faces: MOSHII_ERR_ARG; a null dist or a negative
+ * size: MOSHII_ERR_ARG; F == 0 or N == 0: MOSHII_OK, nothing launched. */
+int moshii_surface_distance_f32(moshii_model_t m, int32_t F, const float* verts, int32_t N, const float* points,
+                                float* dist, int32_t* face /* or NULL */, int32_t* part /* or NULL */, float* nearest /* or NULL */,
+                                uint32_t flags, void* stream);
+int moshii_surface_distance_f64(moshii_model_t m, int32_t F, const double* verts, int32_t N, const double* points,
+                                double* dist, int32_t* face /* or NULL */, int32_t* part /* or NULL */, double* nearest /* or NULL */,
+                                uint32_t flags, void* stream);
+
+/* The same against the meshes of F solved frames, which never leave the device: exported into the handle's scratch a batch at a time
+ * exactly as moshii_virtual_markers_* does (same kernels, same batch sizing and MOSHII_VM_BATCH, same `shape` rules, one call per handle
+ * at a time); points[F][N][3] are the observed markers of each frame (NaN where one is missing).  F x N results reach the caller. */
+int moshii_marker_surface_distance_f32(moshii_model_t m, int32_t F, const float* pose, const float* trans, const float* shape /* or NULL */,
+                                       int32_t N, const float* points, float* dist, int32_t* face /* or NULL */, int32_t* part /* or NULL */,
+                                       float* nearest /* or NULL */, uint32_t flags, void* stream);
+int moshii_marker_surface_distance_f64(moshii_model_t m, int32_t F, const double* pose, const double* trans, const double* shape /* or NULL */,
+                                       int32_t N, const double* points, double* dist, int32_t* face /* or NULL */, int32_t* part /* or NULL */,
+                                       double* nearest /* or NULL */, uint32_t flags, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Pose prior. Replaces create_gmm_body_prior / MaxMixtureComplete
  * (src/moshpp/prior/gmm_prior_ch.py:42-134).  The caller passes the already prepared arrays:
  * means[G][npose], chols[G][npose][npose] (lower Cholesky factors of the precisions, :122-123) and the
  * re-normalised weights[G] (:126-130).

@@ -97,6 +97,14 @@ EXPORTS = {
                                              C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     'moshii_virtual_markers_f64': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    'moshii_surface_distance_f32': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_uint32, C.c_void_p]),
+    'moshii_surface_distance_f64': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_uint32, C.c_void_p]),
+    'moshii_marker_surface_distance_f32': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    'moshii_marker_surface_distance_f64': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     'moshii_prior_create': (C.c_int, [C.c_int32, C.c_int32, _c_double_p, _c_double_p, _c_double_p, C.POINTER(C.c_void_p)]),
     'moshii_prior_destroy': (C.c_int, [C.c_void_p]),
     'moshii_attach_create': (C.c_int, [C.c_void_p, C.c_int32, _c_int_p, _c_double_p, C.POINTER(C.c_void_p)]),
@@ -205,6 +213,20 @@ class DeviceBuffer:
             self.close()
         except Exception:
             pass
+
+
+class SurfaceDistance:
+    """What Model.surface_distance / marker_surface_distance return: distance[F, N] (signed, metres), face[F, N], part[F, N]
+    (0 interior, 1-3 edges ab / bc / ca, 4-6 vertices a / b / c; -1 for an absent point), nearest[F, N, 3]."""
+    __slots__ = ('distance', 'face', 'part', 'nearest')
+
+    def __init__(self, distance, face, part, nearest):
+        self.distance, self.face, self.part, self.nearest = distance, face, part, nearest
+
+    @classmethod
+    def empty(cls, F, N, dtype):
+        return cls(np.zeros((F, N), dtype=dtype), np.zeros((F, N), dtype=np.int32), np.zeros((F, N), dtype=np.int32),
+                   np.zeros((F, N, 3), dtype=dtype))
 
 
 class Model:
@@ -379,6 +401,77 @@ class Model:
         fn = load().moshii_virtual_markers_f32 if f32 else load().moshii_virtual_markers_f64
         check(fn(self.handle, F, pose_ptr, trans_ptr, shape_ptr, len(vids), vids.ctypes.data, dist.ctypes.data, out_ptr, normals_ptr,
                  BUFFERS_DEVICE, stream))
+
+    # ---- signed point-to-mesh distance ----
+    def _check_points(self, points, F, dtype, who):
+        """points[F, N, 3] (or [N, 3] with F == 1) as a contiguous array of `dtype`; NaN rows are absent points."""
+        points = np.asarray(points)
+        if points.ndim == 2 and F == 1:
+            points = points[None]
+        if points.ndim != 3 or points.shape[0] != F or points.shape[2] != 3:
+            raise ValueError(f'{who}: points must be [F, N, 3] = [{F}, N, 3], got {tuple(points.shape)}')
+        if not np.issubdtype(points.dtype, np.number) or np.iscomplexobj(points):
+            raise ValueError(f'{who}: points must be real numbers, got dtype {points.dtype}')
+        return np.ascontiguousarray(points, dtype=dtype)
+
+    def surface_distance(self, verts, points, dtype=None):
+        """Signed distance (metres, positive outside) of points[F, N, 3] to the meshes verts[F, V, 3] with the model's faces:
+        SurfaceDistance(distance[F, N], face[F, N], part[F, N], nearest[F, N, 3]).  dtype: numpy float32 or float64 (default: that of
+        verts).  A point with a NaN coordinate is absent: distance NaN, face -1, part -1, nearest NaN."""
+        verts = np.asarray(verts)
+        if dtype is None:
+            dtype = np.float32 if verts.dtype == np.float32 else np.float64
+        if dtype not in (np.float64, np.float32):
+            raise ValueError(f'surface_distance: dtype must be numpy float64 or float32, not {dtype!r}')
+        self._need_faces('surface_distance')
+        v = verts[None] if verts.ndim == 2 else verts
+        if v.ndim != 3 or v.shape[1:] != (self.V, 3):
+            raise ValueError(f'surface_distance: verts must be [F, {self.V}, 3], got {tuple(verts.shape)}')
+        v = np.ascontiguousarray(v, dtype=dtype)
+        F = v.shape[0]
+        points = self._check_points(points, F, dtype, 'surface_distance')
+        res = SurfaceDistance.empty(F, points.shape[1], dtype)
+        fn = load().moshii_surface_distance_f64 if dtype == np.float64 else load().moshii_surface_distance_f32
+        check(fn(self.handle, F, v.ctypes.data, points.shape[1], points.ctypes.data, res.distance.ctypes.data, res.face.ctypes.data,
+                 res.part.ctypes.data, res.nearest.ctypes.data, BUFFERS_HOST, None))
+        return res
+
+    def surface_distance_device(self, F, verts_ptr, N, points_ptr, dist_ptr, face_ptr=None, part_ptr=None, nearest_ptr=None, stream=None,
+                                f32=True):
+        """Device buffers (f32: float, else double; face / part int32); asynchronous on `stream`."""
+        self._need_faces('surface_distance_device')
+        fn = load().moshii_surface_distance_f32 if f32 else load().moshii_surface_distance_f64
+        check(fn(self.handle, F, verts_ptr, N, points_ptr, dist_ptr, face_ptr, part_ptr, nearest_ptr, BUFFERS_DEVICE, stream))
+
+    def marker_surface_distance(self, pose, trans, points, shape=None, dtype=np.float64):
+        """surface_distance of points[F, N, 3] against the meshes of pose[F, NP], trans[F, 3] (shape as in lbs_forward) -- the meshes
+        never leave the device."""
+        if dtype not in (np.float64, np.float32):
+            raise ValueError(f'marker_surface_distance: dtype must be numpy float64 or float32, not {dtype!r}')
+        self._need_faces('marker_surface_distance')
+        pose = np.ascontiguousarray(np.atleast_2d(pose), dtype=dtype)
+        trans = np.ascontiguousarray(np.atleast_2d(trans), dtype=dtype)
+        F = pose.shape[0]
+        if pose.shape != (F, self.NP) or trans.shape != (F, 3):
+            raise ValueError(f'marker_surface_distance: pose / trans must be [F, {self.NP}] / [F, 3], got {pose.shape} / {trans.shape}')
+        if shape is not None:
+            shape = self._check_shape_rows(shape, F, dtype)
+        points = self._check_points(points, F, dtype, 'marker_surface_distance')
+        res = SurfaceDistance.empty(F, points.shape[1], dtype)
+        fn = load().moshii_marker_surface_distance_f64 if dtype == np.float64 else load().moshii_marker_surface_distance_f32
+        check(fn(self.handle, F, pose.ctypes.data, trans.ctypes.data, shape.ctypes.data if shape is not None else None, points.shape[1],
+                 points.ctypes.data, res.distance.ctypes.data, res.face.ctypes.data, res.part.ctypes.data, res.nearest.ctypes.data,
+                 BUFFERS_HOST, None))
+        return res
+
+    def marker_surface_distance_device(self, F, pose_ptr, trans_ptr, N, points_ptr, dist_ptr, face_ptr=None, part_ptr=None, nearest_ptr=None,
+                                       stream=None, f32=True, shape_ptr=None):
+        """Device buffers for pose / trans / shape / points and the results; asynchronous on `stream`."""
+        self._need_faces('marker_surface_distance_device')
+        if shape_ptr is not None and int(getattr(self, 'n_free_shape', 0)) <= 0:
+            raise ValueError('marker_surface_distance_device: shape_ptr given, but the model has no free shape block (set_free_shape)')
+        fn = load().moshii_marker_surface_distance_f32 if f32 else load().moshii_marker_surface_distance_f64
+        check(fn(self.handle, F, pose_ptr, trans_ptr, shape_ptr, N, points_ptr, dist_ptr, face_ptr, part_ptr, nearest_ptr, BUFFERS_DEVICE, stream))
 
     def lbs_forward_with_normals(self, pose, trans, dtype=np.float32, shape=None):
         """(verts, normals), both [F, V, 3]: the export into a device buffer, the normals from that buffer, two copies back -- the

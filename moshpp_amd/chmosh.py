@@ -247,6 +247,82 @@ class StageIISolver:
         return self.dev.virtual_markers(out['pose'], out['trans'], vids, dist, dtype=dtype, shape=out['shape'] if self.n_shape else None,
                                         return_normals=return_normals)
 
+    def marker_skin_distance(self, out, obs=None, vis=None, labels=None, dtype=np.float32):
+        """capi.SurfaceDistance of the observed markers against the solved skin, frame by frame (the reference's
+        PtsToMesh(signed=True), scan2mesh/mesh_distance_main.py:158-297): distance[F, M] signed, in metres, NaN where a marker is not
+        observed -- on the solver's own handle, the meshes stay on the device.  The observations: obs[F, M, 3] (and vis[F, M]) as
+        solve() took them, or the ragged per-frame lists out['markers_obs'] / out['labels_obs'] laid out over `labels`."""
+        for k in ('pose', 'trans') + (('shape',) if self.n_shape else ()):
+            if k not in out:
+                raise KeyError(f"StageIISolver.marker_skin_distance: the result has no '{k}'")
+        if getattr(self.sm, 'f', None) is None:
+            raise ValueError('StageIISolver.marker_skin_distance: the surface model has no faces (f)')
+        F = np.atleast_2d(out['pose']).shape[0]
+        if obs is None:
+            for k in ('markers_obs', 'labels_obs'):
+                if k not in out:
+                    raise KeyError(f"StageIISolver.marker_skin_distance: no obs given and the result has no '{k}'")
+            if labels is None:
+                raise ValueError('StageIISolver.marker_skin_distance: the ragged markers_obs / labels_obs need the label order (labels)')
+            points = pack_observed_markers(out['markers_obs'], out['labels_obs'], labels)
+        else:
+            points = np.array(obs, dtype=np.float64)
+            if vis is not None:
+                points[~np.asarray(vis, dtype=bool)] = np.nan
+        if points.ndim != 3 or points.shape[0] != F or points.shape[2] != 3:
+            raise ValueError(f'StageIISolver.marker_skin_distance: the observations are {points.shape}, the result has {F} frames')
+        if not getattr(self.dev, 'n_faces', 0):
+            self.dev.set_faces(self.sm.f)
+        return self.dev.marker_surface_distance(out['pose'], out['trans'], points, shape=out['shape'] if self.n_shape else None, dtype=dtype)
+
+
+def pack_observed_markers(markers_obs, labels_obs, labels, frame_ids=None):
+    """points[T, M, 3]: the per-frame ragged lists a Stage-II result stores (markers_obs[f][j] is the marker labels_obs[f][j]) laid out
+    over `labels`, NaN where a label is not observed on a frame.  frame_ids: rows of the result, in that order (repeats allowed)."""
+    if len(markers_obs) != len(labels_obs):
+        raise ValueError(f'markers_obs has {len(markers_obs)} frames, labels_obs {len(labels_obs)}')
+    labels = list(labels)
+    col = {l: i for i, l in enumerate(labels)}
+    if len(col) != len(labels):
+        raise ValueError('the label order names a label twice')
+    T = len(markers_obs)
+    ids = np.arange(T) if frame_ids is None else np.atleast_1d(np.asarray(frame_ids))
+    if ids.ndim != 1 or (len(ids) and not np.issubdtype(ids.dtype, np.integer)):
+        raise ValueError('frame_ids must be a list of integers')
+    if len(ids) and (ids.min() < 0 or ids.max() >= T):
+        raise IndexError(f'frame_ids outside the {T} solved frames')
+    for f in range(T):
+        m = np.asarray(markers_obs[f], dtype=np.float64)
+        if m.size == 0:
+            m = m.reshape(0, 3)
+        if m.ndim != 2 or m.shape[1] != 3 or len(m) != len(labels_obs[f]):
+            raise ValueError(f'frame {f}: markers_obs is {m.shape}, labels_obs names {len(labels_obs[f])} markers')
+        for l in labels_obs[f]:
+            if l not in col:
+                raise ValueError(f"frame {f}: observed label '{l}' is not among the {len(labels)} labels")
+    out = np.full((len(ids), len(labels), 3), np.nan)
+    for r, f in enumerate(ids):
+        if len(labels_obs[f]):
+            out[r, [col[l] for l in labels_obs[f]]] = np.asarray(markers_obs[f], dtype=np.float64)
+    return out
+
+
+def skin_distance_summary(distance, labels):
+    """Per label, from distance[T, M] (signed metres, NaN where unobserved): the count of observed frames, the median / 5th / 95th
+    percentile of the distance and the share of observed frames with a negative distance (NaN for a label never observed)."""
+    d = np.asarray(distance, dtype=np.float64)
+    if d.ndim != 2 or d.shape[1] != len(labels):
+        raise ValueError(f'distance is {d.shape}, expected [T, {len(labels)}]')
+    out = {}
+    for i, l in enumerate(labels):
+        x = d[:, i][np.isfinite(d[:, i])]
+        if len(x):
+            p5, med, p95 = np.percentile(x, [5, 50, 95])
+            out[l] = dict(count=int(len(x)), median=float(med), p5=float(p5), p95=float(p95), negative_share=float((x < 0).mean()))
+        else:
+            out[l] = dict(count=0, median=np.nan, p5=np.nan, p95=np.nan, negative_share=np.nan)
+    return out
+
 
 def mosh_stageii(mocap_fname: str, cfg, markers_latent: np.ndarray, latent_labels: list, betas: np.ndarray,
                  marker_meta: dict, v_template_fname=None) -> dict:

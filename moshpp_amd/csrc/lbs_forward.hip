@@ -1128,6 +1128,212 @@ __global__ __launch_bounds__(256) void k_vn_markers(int V, int nf, int M, const 
     }
 }
 
+// ---- signed point-to-mesh distance of posed meshes (moshii_surface_distance_*, moshii_marker_surface_distance_*) ----
+// The reference's PtsToMesh(signed=True) (scan2mesh/mesh_distance_main.py:158-297) for every point of every frame, exhaustive over the
+// triangles: nearest triangle by the region tests of closest_on_tri (stagei.hip) / the oracle's _closest_on_triangles, ties to the
+// lowest face id, sign from (p - nearest) . n with n the face normal (interior), the vertex normal (vertex) or the sum of the two
+// vertex normals (edge).  Two steps:
+//   search   k_sd_lds / k_sd_gather: a wave takes SD_PB points of one frame, its lanes deal the triangles among themselves, every
+//            lane keeps (d^2, face id) per point in the call's precision, and the wave's lexicographic minimum (shuffles) is the
+//            winner: d^2 first, then the id, so no order of arrival decides a tie.  Only the winner's id leaves the search.
+//   finish   k_sd_finish: one quad per point evaluates the winner once in f64 from the inputs as given (closest point, part, the
+//            part's normals through the CSR rows of the normals kernels, sign, distance) and rounds once on the store.
+// Every product of the search is taken between DIFFERENCES of the inputs (b - a, c - a, p - a; the residual p - q = ap - s ab - t ac),
+// so its error scales with the distances involved, not with where the frame stands: the frames are staged as they are, uncentred.
+// All of it in explicit fma / single operations: the two f32 searches give the same d^2 bits for a (point, triangle) whatever the
+// compiler contracts elsewhere, hence the same winners.
+#define SD_THREADS 1024                  // k_sd_lds: 16 waves
+#define SD_NOFACE 0x7fffffff
+
+__device__ __forceinline__ float sd_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+__device__ __forceinline__ double sd_rcp(double x) { return 1.0 / x; }
+__device__ __forceinline__ float sd_fma(float a, float b, float c) { return fmaf(a, b, c); }
+__device__ __forceinline__ double sd_fma(double a, double b, double c) { return fma(a, b, c); }
+template <class T>
+__device__ __forceinline__ T sd_dot(const T* a, const T* b) { return sd_fma(a[2], b[2], sd_fma(a[1], b[1], a[0] * b[0])); }
+
+// closest point of the triangle (a, a + ab, a + ac) to a + ap as q = a + s ab + t ac; returns the part code (0 interior, 1 ab, 2 bc,
+// 3 ca, 4 a, 5 b, 6 c) by the oracle's order of tests.  e00 = ab.ab, e01 = ab.ac, e11 = ac.ac.  A triangle without area gives NaN.
+template <class T>
+__device__ __forceinline__ int sd_closest(const T* ab, const T* ac, T e00, T e01, T e11, const T* ap, T* s, T* t) {
+    const T d1 = sd_dot(ab, ap), d2 = sd_dot(ac, ap);
+    const T d3 = d1 - e00, d4 = d2 - e01, d5 = d1 - e01, d6 = d2 - e11;     // ab.bp, ac.bp, ab.cp, ac.cp
+    const T vc = sd_fma(d1, d4, -(d3 * d2)), vb = sd_fma(d5, d2, -(d1 * d6)), va = sd_fma(d3, d6, -(d5 * d4));
+    const T d43 = d4 - d3, d56 = d5 - d6;
+    const int part = (d1 <= 0 && d2 <= 0) ? 4 : (d3 >= 0 && d4 <= d3) ? 5 : (vc <= 0 && d1 >= 0 && d3 <= 0) ? 1 : (d6 >= 0 && d5 <= d6) ? 6
+                   : (vb <= 0 && d2 >= 0 && d6 <= 0) ? 3 : (va <= 0 && d43 >= 0 && d56 >= 0) ? 2 : 0;
+    const T den = part == 1 ? d1 - d3 : part == 3 ? d2 - d6 : part == 2 ? d43 + d56 : part == 0 ? (va + vb) + vc : (T)1;
+    const T r = sd_rcp(den);
+    const T u = d43 * r;                                                     // (part 2: q = b + u (c - b))
+    *s = part == 5 ? (T)1 : part == 1 ? d1 * r : part == 2 ? (T)1 - u : part == 0 ? vb * r : (T)0;
+    *t = part == 6 ? (T)1 : part == 3 ? d2 * r : part == 2 ? u : part == 0 ? vc * r : (T)0;
+    return part;
+}
+
+__device__ __forceinline__ void sd_face_ids(const unsigned* __restrict__ tris, bool w16, unsigned f, unsigned* ia, unsigned* ib, unsigned* ic) {
+    if (w16) {   // four 16-bit fields a face (the fourth unused): one 8-byte load
+        const unsigned long long w = reinterpret_cast<const unsigned long long*>(tris)[f];
+        *ia = (unsigned)w & 0xffffu; *ib = ((unsigned)w >> 16) & 0xffffu; *ic = (unsigned)(w >> 32) & 0xffffu;
+    }
+    else { *ia = tris[3 * (size_t)f]; *ib = tris[3 * (size_t)f + 1]; *ic = tris[3 * (size_t)f + 2]; }
+}
+
+// One wave: the nearest triangle of each of the np <= PB points pts[0 .. np) (x, y, z apiece) on the mesh fr ([V][3], LDS or global),
+// written to win[0 .. np) by lane 0: SD_NOFACE for an absent point (a non-finite coordinate: it costs no test) and where no triangle
+// has a distance.  EVERY lane of the wave calls this.
+template <class T, int PB, bool W16>
+__device__ __forceinline__ void sd_search(const T* fr, int NF, const unsigned* __restrict__ tris, const T* __restrict__ pts, int np, int lane, int* win) {
+    T p[PB][3], best[PB];
+    int bid[PB];
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < PB; ++k) {
+        bool ok = k < np;
+        for (int i = 0; i < 3; ++i) { p[k][i] = ok ? pts[3 * k + i] : (T)0; ok = ok && p[k][i] - p[k][i] == (T)0; }   // (x - x: NaN for NaN and the infinities)
+        // (an absent point keeps a NaN coordinate: its d^2 is NaN and never passes `<`)
+        if (!ok) p[k][0] = (T)NAN;
+        any = any || ok;
+        best[k] = (T)INFINITY; bid[k] = SD_NOFACE;
+    }
+    if (any)
+        for (int f = lane; f < NF; f += 64) {
+            unsigned ia, ib, ic;
+            sd_face_ids(tris, W16, (unsigned)f, &ia, &ib, &ic);
+            if (ia == ib || ib == ic || ia == ic) continue;               // a face that names a vertex twice never wins
+            T a[3], ab[3], ac[3];
+            for (int i = 0; i < 3; ++i) { a[i] = fr[3 * ia + i]; ab[i] = fr[3 * ib + i] - a[i]; ac[i] = fr[3 * ic + i] - a[i]; }
+            const T e00 = sd_dot(ab, ab), e01 = sd_dot(ab, ac), e11 = sd_dot(ac, ac);
+            // the triangle's normal: (s, t) are solved for the point's FOOT on the plane, ap - h n, so that the dot products the region
+            // tests multiply stay as small as the in-plane offsets -- a point a metre off a centimetre triangle would otherwise lose
+            // the digits its coefficients live in.  The residual below is taken from ap itself.
+            const T n[3] = {sd_fma(ab[1], ac[2], -(ab[2] * ac[1])), sd_fma(ab[2], ac[0], -(ab[0] * ac[2])), sd_fma(ab[0], ac[1], -(ab[1] * ac[0]))};
+            const T nn = sd_dot(n, n), rn = nn > (T)0 ? sd_rcp(nn) : (T)0;
+#pragma unroll
+            for (int k = 0; k < PB; ++k) {
+                T ap[3], apl[3], s, t, df[3];
+                for (int i = 0; i < 3; ++i) ap[i] = p[k][i] - a[i];
+                const T h = sd_dot(ap, n) * rn;
+                for (int i = 0; i < 3; ++i) apl[i] = sd_fma(-h, n[i], ap[i]);
+                const int part = sd_closest(ab, ac, e00, e01, e11, apl, &s, &t);
+                for (int i = 0; i < 3; ++i) df[i] = sd_fma(-t, ac[i], sd_fma(-s, ab[i], ap[i]));
+                // above the interior the distance is the height alone: (s, t) of a thin triangle would add an in-plane residual
+                const T dd = part == 0 ? h * h * nn : sd_dot(df, df);
+                if (dd < best[k]) { best[k] = dd; bid[k] = f; }           // (a lane's ids ascend: `<` keeps its lowest on a tie)
+            }
+        }
+#pragma unroll
+    for (int k = 0; k < PB; ++k) {
+        if (any)
+            for (int off = 32; off > 0; off >>= 1) {
+                const T od = __shfl_down(best[k], off);
+                const int oi = __shfl_down(bid[k], off);
+                if (od < best[k] || (od == best[k] && oi < bid[k])) { best[k] = od; bid[k] = oi; }
+            }
+        if (lane == 0 && k < np) win[k] = bid[k];
+    }
+}
+
+// The staged f32 search (MOSHII_SD_KERNEL=lds; not the default, see moshii_launch_surface_distance): a workgroup keeps G whole frames in LDS (the copy of k_vn_lds), its 16 waves take the (frame, group of PB points)
+// pairs in turn; the face table is the same for every frame and comes through L2.
+template <int PB, bool W16>
+__global__ __launch_bounds__(SD_THREADS) void k_sd_lds(int V, int NF, int F, int G, int N, const float* __restrict__ verts,
+                                                        const float* __restrict__ points, const unsigned* __restrict__ tris, int* __restrict__ win) {
+    extern __shared__ __attribute__((aligned(16))) float smf[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned fv = (unsigned)V * 3;
+    const int ngrp = (N + PB - 1) / PB;
+    for (int fb = blockIdx.x * G; fb < F; fb += gridDim.x * G) {
+        const int ng = min(G, F - fb);
+        const float* src = verts + (size_t)fb * fv;
+        const unsigned n = (unsigned)ng * fv;
+        const unsigned a = (unsigned)(((size_t)src >> 2) & 3), head = ((4u - a) & 3u) < n ? ((4u - a) & 3u) : n, n4 = (n - head) >> 2, tail = n - head - 4 * n4;
+        for (unsigned i = tid; i < n4; i += SD_THREADS)
+            *reinterpret_cast<f32x4*>(smf + a + head + 4 * i) = *reinterpret_cast<const f32x4*>(src + head + 4 * i);
+        if ((unsigned)tid < head) smf[a + tid] = src[tid];
+        if ((unsigned)tid < tail) smf[a + head + 4 * n4 + tid] = src[head + 4 * n4 + tid];
+        __syncthreads();
+        for (int it = wave; it < ng * ngrp; it += SD_THREADS / 64) {
+            const int fl = it / ngrp, g = it - fl * ngrp;
+            const size_t at = (size_t)(fb + fl) * N + (size_t)g * PB;
+            sd_search<float, PB, W16>(smf + a + (unsigned)fl * fv, NF, tris, points + 3 * at, min(PB, N - g * PB), lane, win + at);
+        }
+        __syncthreads();
+    }
+}
+
+// The same search with the vertices read through L2: the default of both precisions.
+// A workgroup = 4 waves, a wave per (frame, group of PB points), walked with the grid's stride.
+template <class T, int PB, bool W16>
+__global__ __launch_bounds__(256) void k_sd_gather(int V, int NF, long long F, int N, const T* __restrict__ verts, const T* __restrict__ points,
+                                                    const unsigned* __restrict__ tris, int* __restrict__ win) {
+    const int lane = threadIdx.x & 63;
+    const long long ngrp = (N + PB - 1) / PB, items = F * ngrp;
+    for (long long it = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); it < items; it += (long long)gridDim.x * 4) {
+        const long long f = it / ngrp;
+        const int g = (int)(it - f * ngrp);
+        const size_t at = (size_t)f * N + (size_t)g * PB;
+        sd_search<T, PB, W16>(verts + (size_t)f * V * 3, NF, tris, points + 3 * at, min(PB, N - g * PB), lane, win + at);
+    }
+}
+
+// The winners in f64, one quad per point: total = F x N points, face[] holds the search's winner on entry and the face id (or -1)
+// on return; part / nearest may be null.
+template <class T, bool W16>
+__global__ __launch_bounds__(256) void k_sd_finish(int V, long long total, int N, const T* __restrict__ verts, const T* __restrict__ points,
+                                                    const unsigned* __restrict__ tris, const unsigned* __restrict__ rows,
+                                                    const unsigned* __restrict__ pairs, T* __restrict__ dist, int* face, int* __restrict__ part,
+                                                    T* __restrict__ nearest) {
+    const int tid = threadIdx.x, sub = tid & 3;
+    for (long long i0 = (long long)blockIdx.x * 64; i0 < total; i0 += (long long)gridDim.x * 64) {
+        const long long item = i0 + (tid >> 2);
+        const bool in = item < total;
+        const int w = in ? face[item] : SD_NOFACE;
+        const bool found = in && w != SD_NOFACE;
+        const T* fr = verts + (size_t)(in ? item / N : 0) * V * 3;
+        double p[3] = {0, 0, 0}, a[3] = {0, 0, 0}, ab[3] = {0, 0, 0}, ac[3] = {0, 0, 0}, ap[3], s = 0, t = 0;
+        unsigned id[3] = {0, 0, 0};
+        int pc = -1;
+        if (found) {
+            sd_face_ids(tris, W16, (unsigned)w, &id[0], &id[1], &id[2]);
+            for (int i = 0; i < 3; ++i) {
+                p[i] = (double)points[(size_t)item * 3 + i];
+                a[i] = (double)fr[3 * (size_t)id[0] + i];
+                ab[i] = (double)fr[3 * (size_t)id[1] + i] - a[i];
+                ac[i] = (double)fr[3 * (size_t)id[2] + i] - a[i];
+            }
+            for (int i = 0; i < 3; ++i) ap[i] = p[i] - a[i];
+            pc = sd_closest(ab, ac, sd_dot(ab, ab), sd_dot(ab, ac), sd_dot(ac, ac), ap, &s, &t);
+        }
+        // the normals of the part: none (interior), one vertex, or the two ends of an edge -- the quad walks their rows together
+        const bool one = found && pc > 0;
+        const bool two = found && pc > 0 && pc <= 3;
+        const int k0 = pc > 3 ? pc - 4 : pc - 1, k1 = pc % 3;
+        const unsigned v0 = one ? (k0 == 0 ? id[0] : k0 == 1 ? id[1] : id[2]) : 0u, v1 = two ? (k1 == 0 ? id[0] : k1 == 1 ? id[1] : id[2]) : 0u;
+        double n0[3], n1[3], pos[3];
+        vn_vertex<double, T, W16>(fr, v0, sub, one, rows, pairs, n0, pos);
+        vn_vertex<double, T, W16>(fr, v1, sub, two, rows, pairs, n1, pos);
+        if (!in || sub != 0) continue;
+        if (!found) {
+            dist[item] = (T)NAN; face[item] = -1;
+            if (part) part[item] = -1;
+            if (nearest) for (int i = 0; i < 3; ++i) nearest[(size_t)item * 3 + i] = (T)NAN;
+            continue;
+        }
+        double df[3], q[3], nn[3];
+        for (int i = 0; i < 3; ++i) {
+            const double off = sd_fma(t, ac[i], s * ab[i]);
+            q[i] = a[i] + off; df[i] = ap[i] - off;
+        }
+        if (pc == 0) { nn[0] = ab[1] * ac[2] - ab[2] * ac[1]; nn[1] = ab[2] * ac[0] - ab[0] * ac[2]; nn[2] = ab[0] * ac[1] - ab[1] * ac[0]; }
+        else for (int i = 0; i < 3; ++i) nn[i] = two ? n0[i] + n1[i] : n0[i];
+        const double sd = sd_dot(df, nn);
+        const double dir = sd > 0 ? 1.0 : sd < 0 ? -1.0 : 0.0;
+        dist[item] = (T)(sqrt(sd_dot(df, df)) * dir);
+        if (part) part[item] = pc;
+        if (nearest) for (int i = 0; i < 3; ++i) nearest[(size_t)item * 3 + i] = (T)q[i];
+    }
+}
+
 }  // namespace
 
 static void free_ptr(void* p) { if (p) hipFree(p); }
@@ -1535,4 +1741,86 @@ extern "C" hipError_t moshii_launch_marker_normals(hipStream_t stream, int V, in
         else hipLaunchKernelGGL((k_vn_markers<float, false>), grid, dim3(256), 0, stream, V, nf, M, (const float*)verts, vids, dist, (float*)markers, (float*)mnormals, rows, pairs);
     }
     return hipGetLastError();
+}
+
+// ---- signed point-to-mesh distance: launches (the handle, its tables and the checks live in moshii_api.hip) ----
+// face[F x N] receives the search's winners and then the face ids: never null here.  tris: the handle's face table (four 16-bit
+// fields a face while w16, else three 32-bit ids).  *which: the search kernel taken.
+template <class T, int PB>
+static hipError_t sd_launch_gather(hipStream_t stream, int V, int NF, long long F, int N, const T* verts, const T* points,
+                                   const unsigned* tris, int w16, int* face) {
+    const long long items = F * ((N + PB - 1) / PB);
+    const dim3 grid((unsigned)std::min<long long>((items + 3) / 4, 1 << 20));
+    if (w16) hipLaunchKernelGGL((k_sd_gather<T, PB, true>), grid, dim3(256), 0, stream, V, NF, F, N, verts, points, tris, face);
+    else hipLaunchKernelGGL((k_sd_gather<T, PB, false>), grid, dim3(256), 0, stream, V, NF, F, N, verts, points, tris, face);
+    return hipGetLastError();
+}
+template <int PB>
+static hipError_t sd_launch_lds(hipStream_t stream, int V, int NF, int F, int G, int N, int grid, size_t lds, const float* verts,
+                                const float* points, const unsigned* tris, int w16, int* face) {
+    const void* kern = w16 ? reinterpret_cast<const void*>(k_sd_lds<PB, true>) : reinterpret_cast<const void*>(k_sd_lds<PB, false>);
+    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);   // (the opt-in above 64 KB)
+    if (e != hipSuccess) return e;
+    if (w16) hipLaunchKernelGGL((k_sd_lds<PB, true>), dim3(grid), dim3(SD_THREADS), lds, stream, V, NF, F, G, N, verts, points, tris, face);
+    else hipLaunchKernelGGL((k_sd_lds<PB, false>), dim3(grid), dim3(SD_THREADS), lds, stream, V, NF, F, G, N, verts, points, tris, face);
+    return hipGetLastError();
+}
+template <class T>
+static hipError_t sd_launch_finish(hipStream_t stream, int V, long long total, int N, const T* verts, const T* points, const unsigned* tris,
+                                   int w16, const unsigned* rows, const unsigned* pairs, T* dist, int* face, int* part, T* nearest) {
+    const dim3 grid((unsigned)std::min<long long>((total + 63) / 64, 1 << 20));
+    if (w16) hipLaunchKernelGGL((k_sd_finish<T, true>), grid, dim3(256), 0, stream, V, total, N, verts, points, tris, rows, pairs, dist, face, part, nearest);
+    else hipLaunchKernelGGL((k_sd_finish<T, false>), grid, dim3(256), 0, stream, V, total, N, verts, points, tris, rows, pairs, dist, face, part, nearest);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t moshii_launch_surface_distance(hipStream_t stream, int V, int NF, int F, int N, int f64, const void* verts,
+                                                     const void* points, const unsigned* tris, int w16, const unsigned* rows,
+                                                     const unsigned* pairs, void* dist, int* face, int* part, void* nearest,
+                                                     const char** which, int* lds_bytes, int* threads) {
+    const char* none = nullptr;
+    int i0 = 0, i1 = 0;
+    if (!which) which = &none;
+    if (!lds_bytes) lds_bytes = &i0;
+    if (!threads) threads = &i1;
+    *which = ""; *lds_bytes = 0; *threads = 256;
+    if (F <= 0 || N <= 0 || V <= 0) return hipSuccess;
+    const long long total = (long long)F * N;
+    // points a wave takes together (a triangle is loaded once for all of them): four where that still leaves a workgroup's waves busy
+    const bool pb4 = N > 16;
+    hipError_t e;
+    if (f64) {
+        *which = "k_sd_gather<double>";
+        e = pb4 ? sd_launch_gather<double, 4>(stream, V, NF, F, N, (const double*)verts, (const double*)points, tris, w16, face)
+                : sd_launch_gather<double, 1>(stream, V, NF, F, N, (const double*)verts, (const double*)points, tris, w16, face);
+        if (e != hipSuccess) return e;
+        return sd_launch_finish<double>(stream, V, total, N, (const double*)verts, (const double*)points, tris, w16, rows, pairs, (double*)dist, face, part, (double*)nearest);
+    }
+    // The L2 kernel is the default for f32 too: measured on 4000 SMPL-H frames x 53 points it takes 7.4 ms where the staged kernel takes
+    // 11.6 (profiles/surface_distance.txt).  MOSHII_SD_KERNEL=lds asks for the staged kernel where a frame fits
+    // (tests, tools/lbs_bench.py --surface-distance); same bits either way.
+    const char* ek = getenv("MOSHII_SD_KERNEL");
+    const size_t frame = (size_t)V * 12;
+    if (!(ek && !strcmp(ek, "lds")) || frame + 16 > VN_LDS_MAX) {
+        *which = "k_sd_gather<float>";
+        e = pb4 ? sd_launch_gather<float, 4>(stream, V, NF, F, N, (const float*)verts, (const float*)points, tris, w16, face)
+                : sd_launch_gather<float, 1>(stream, V, NF, F, N, (const float*)verts, (const float*)points, tris, w16, face);
+    } else {
+        int ncu = 0, devid = 0;
+        hipGetDevice(&devid);
+        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, devid);
+        if (ncu <= 0) ncu = 256;
+        // frames a workgroup keeps resident, as the normals kernel sizes them: a big body one, a small body as many as leave room for a
+        // second workgroup on the CU, but no more than spread the call over every CU twice
+        int G = 1;
+        if (frame + 16 <= VN_LDS_PAIR) G = (int)std::max<size_t>(1, std::min<size_t>((VN_LDS_PAIR - 16) / frame, ((size_t)F + 2 * ncu - 1) / (2 * ncu)));
+        const size_t lds = (((size_t)G * V * 3 + 3) * sizeof(float) + 15) & ~(size_t)15;
+        const int per_cu = lds <= VN_LDS_PAIR ? 2 : 1;
+        const int grid = (int)std::min<long long>(((long long)F + G - 1) / G, (long long)per_cu * ncu);
+        *which = "k_sd_lds"; *lds_bytes = (int)lds; *threads = SD_THREADS;
+        e = pb4 ? sd_launch_lds<4>(stream, V, NF, F, G, N, grid, lds, (const float*)verts, (const float*)points, tris, w16, face)
+                : sd_launch_lds<1>(stream, V, NF, F, G, N, grid, lds, (const float*)verts, (const float*)points, tris, w16, face);
+    }
+    if (e != hipSuccess) return e;
+    return sd_launch_finish<float>(stream, V, total, N, (const float*)verts, (const float*)points, tris, w16, rows, pairs, (float*)dist, face, part, (float*)nearest);
 }

@@ -27,6 +27,10 @@ extern "C" hipError_t moshii_launch_vertex_normals(hipStream_t stream, int V, in
 extern "C" hipError_t moshii_launch_marker_normals(hipStream_t stream, int V, int nf, int M, int f64, const void* verts, const int* vids,
                                                    const double* dist, void* markers, void* mnormals, const unsigned* rows,
                                                    const unsigned* pairs, int w16);
+extern "C" hipError_t moshii_launch_surface_distance(hipStream_t stream, int V, int NF, int F, int N, int f64, const void* verts,
+                                                     const void* points, const unsigned* tris, int w16, const unsigned* rows,
+                                                     const unsigned* pairs, void* dist, int* face, int* part, void* nearest,
+                                                     const char** which, int* lds_bytes, int* threads);
 
 namespace {
 
@@ -95,6 +99,10 @@ struct moshii_model_s {
     unsigned *d_vn_rows = nullptr, *d_vn_pairs = nullptr;
     int vn_w16 = 0;
     Scratch vmscratch;                  // moshii_virtual_markers_*: a batch of full meshes + the marker ids and distances
+    // the triangles themselves for moshii_surface_distance_* (four 16-bit fields a face while vn_w16, else three 32-bit ids)
+    unsigned* d_sd_tris = nullptr;
+    int n_faces = 0;
+    Scratch sdscratch;                  // moshii_surface_distance_* without a `face` output: the search's winners
     ModelDev dev() const {
         ModelDev md;
         md.V = V; md.K = K; md.P = P; md.NP = NP; md.body_dof = body_dof; md.hand_dof = hand_dof;
@@ -370,7 +378,7 @@ struct LaunchInfo { std::string name; int lds = 0; int threads = 0; } g_last;
 extern "C" {
 
 const char* moshii_last_error(void) { return g_err.c_str(); }
-int moshii_version(void) { return 104; }   // 101: moshii_stagei_desc grew by init_sq; 102: moshii_solve_opts by the joint-angle term; 103: moshii_lbs_forward_shape_*; 104: moshii_model_set_faces, moshii_vertex_normals_*, moshii_virtual_markers_* (include/moshii.h)
+int moshii_version(void) { return 105; }   // 101: moshii_stagei_desc grew by init_sq; 102: moshii_solve_opts by the joint-angle term; 103: moshii_lbs_forward_shape_*; 104: moshii_model_set_faces, moshii_vertex_normals_*, moshii_virtual_markers_*; 105: moshii_surface_distance_*, moshii_marker_surface_distance_* (include/moshii.h)
 #ifndef MOSHII_SRC_HASH
 #define MOSHII_SRC_HASH "unknown"
 #endif
@@ -478,6 +486,7 @@ int moshii_model_destroy(moshii_model_t m) {
     for (void* p : ptrs) if (p) hipFree(p);
     if (m->d_vn_rows) hipFree(m->d_vn_rows);
     if (m->d_vn_pairs) hipFree(m->d_vn_pairs);
+    if (m->d_sd_tris) hipFree(m->d_sd_tris);
     free_l32(m);
     delete m;
     return MOSHII_OK;
@@ -630,6 +639,8 @@ int moshii_model_set_faces(moshii_model_t m, int32_t n_faces, const int32_t* fac
     HIP_TRY(hipDeviceSynchronize());
     if (m->d_vn_rows) { hipFree(m->d_vn_rows); m->d_vn_rows = nullptr; }
     if (m->d_vn_pairs) { hipFree(m->d_vn_pairs); m->d_vn_pairs = nullptr; }
+    if (m->d_sd_tris) { hipFree(m->d_sd_tris); m->d_sd_tris = nullptr; }
+    m->n_faces = 0;
     if (n_faces == 0) return MOSHII_OK;
     // vertex -> incident corners: for vertex v of face (a, b, c) the other two in cyclic order, (p - v) x (q - v) = the face's scaled
     // normal; a face that names a vertex twice has none and is left out
@@ -650,12 +661,21 @@ int moshii_model_set_faces(moshii_model_t m, int32_t n_faces, const int32_t* fac
             else { pairs[2 * at] = p; pairs[2 * at + 1] = q; }
         }
     }
-    // both parts uploaded before either is published: a failure leaves the handle without a table, never with half of one
-    unsigned *d_rows = nullptr, *d_pairs = nullptr;
+    // the triangles as the distance search reads them (every face, the degenerate ones too: face ids are the caller's)
+    std::vector<unsigned> tris((size_t)n_faces * (w16 ? 2 : 3));
+    for (size_t f = 0; f < (size_t)n_faces; ++f) {
+        const int32_t* t = faces + f * 3;
+        if (w16) { tris[2 * f] = (unsigned)t[0] | ((unsigned)t[1] << 16); tris[2 * f + 1] = (unsigned)t[2]; }
+        else for (int c = 0; c < 3; ++c) tris[3 * f + c] = (unsigned)t[c];
+    }
+    // every part uploaded before any is published: a failure leaves the handle without a table, never with half of one
+    unsigned *d_rows = nullptr, *d_pairs = nullptr, *d_tris = nullptr;
     int rc;
     if ((rc = dev_upload(rows.data(), rows.size(), &d_rows))) return rc;
     if ((rc = dev_upload(pairs.data(), pairs.size(), &d_pairs))) { hipFree(d_rows); return rc; }
-    m->d_vn_rows = d_rows; m->d_vn_pairs = d_pairs;
+    if ((rc = dev_upload(tris.data(), tris.size(), &d_tris))) { hipFree(d_rows); hipFree(d_pairs); return rc; }
+    m->d_vn_rows = d_rows; m->d_vn_pairs = d_pairs; m->d_sd_tris = d_tris;
+    m->n_faces = n_faces;
     m->vn_w16 = w16 ? 1 : 0;
     return MOSHII_OK;
 }
@@ -791,6 +811,155 @@ int moshii_virtual_markers_f32(moshii_model_t m, int32_t F, const float* pose, c
 int moshii_virtual_markers_f64(moshii_model_t m, int32_t F, const double* pose, const double* trans, const double* shape, int32_t M,
                                const int32_t* vids, const double* dist, double* markers, double* marker_normals, uint32_t flags, void* stream) {
     return virtual_markers_impl(m, F, pose, trans, shape, M, vids, dist, markers, marker_normals, flags, stream, "moshii_virtual_markers_f64");
+}
+
+}  // extern "C"
+
+// ---- signed point-to-mesh distance (version 105) ----
+namespace {
+const char* sd_check(moshii_model_t m, int32_t F, int32_t N, const void* dist) {
+    if (!m) return "null model";
+    if (F < 0 || N < 0) return "negative F or N";
+    if (!dist) return "dist is null";
+    return nullptr;
+}
+}  // namespace
+
+// verts / points / outputs on the device; `face` may be null (the winners then go to the handle's scratch)
+template <class T>
+static int surface_distance_launch(moshii_model_t m, int F, const T* d_verts, int N, const T* d_points, T* d_dist, int* d_face, int* d_part,
+                                   T* d_near, int* d_win, hipStream_t stream) {
+    const char* which = "";
+    int lds = 0, threads = 0;
+    HIP_TRY(moshii_launch_surface_distance(stream, m->V, m->n_faces, F, N, sizeof(T) == 8, d_verts, d_points, m->d_sd_tris, m->vn_w16, m->d_vn_rows,
+                                           m->d_vn_pairs, d_dist, d_face ? d_face : d_win, d_part, d_near, &which, &lds, &threads));
+    g_last.name = which; g_last.lds = lds; g_last.threads = threads;
+    return MOSHII_OK;
+}
+
+template <class T>
+static int surface_distance_impl(moshii_model_t m, int32_t F, const T* verts, int32_t N, const T* points, T* dist, int32_t* face, int32_t* part,
+                                 T* nearest, uint32_t flags, void* stream_, const char* name) {
+    if (const char* bad = sd_check(m, F, N, dist)) return fail(MOSHII_ERR_ARG, std::string(name) + ": " + bad);
+    if (!m->d_sd_tris) return fail(MOSHII_ERR_ARG, std::string(name) + ": the model has no faces: call moshii_model_set_faces first");
+    if (F == 0 || N == 0) return MOSHII_OK;
+    if (!verts || !points) return fail(MOSHII_ERR_ARG, std::string(name) + ": verts or points is null");
+    hipStream_t stream = (hipStream_t)stream_;
+    const bool dev = (flags & MOSHII_BUFFERS_DEVICE) != 0;
+    const size_t nv = (size_t)F * m->V * 3, np = (size_t)F * N;
+    if (dev) {
+        int* d_win = nullptr;
+        if (!face) {
+            int rc = m->sdscratch.reserve(np * sizeof(int), stream);   // (waits for the call before this one)
+            if (rc) return rc;
+            d_win = reinterpret_cast<int*>(m->sdscratch.ptr);
+        }
+        return surface_distance_launch(m, F, verts, N, points, dist, face, part, nearest, d_win, stream);
+    }
+    DevTemps temps;
+    T *t_verts = nullptr, *t_points = nullptr, *t_dist = nullptr, *t_near = nullptr;
+    int *t_face = nullptr, *t_part = nullptr;
+    int rc = dev_upload(verts, nv, &t_verts); temps.keep(t_verts);
+    if (rc) return rc;
+    rc = dev_upload(points, np * 3, &t_points); temps.keep(t_points);
+    if (rc) return rc;
+    HIP_TRY(hipMalloc((void**)&t_dist, np * sizeof(T))); temps.keep(t_dist);
+    HIP_TRY(hipMalloc((void**)&t_face, np * sizeof(int))); temps.keep(t_face);
+    if (part) { HIP_TRY(hipMalloc((void**)&t_part, np * sizeof(int))); temps.keep(t_part); }
+    if (nearest) { HIP_TRY(hipMalloc((void**)&t_near, np * 3 * sizeof(T))); temps.keep(t_near); }
+    rc = surface_distance_launch(m, F, t_verts, N, t_points, t_dist, t_face, t_part, t_near, (int*)nullptr, stream);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipMemcpy(dist, t_dist, np * sizeof(T), hipMemcpyDeviceToHost));
+    if (face) HIP_TRY(hipMemcpy(face, t_face, np * sizeof(int), hipMemcpyDeviceToHost));
+    if (part) HIP_TRY(hipMemcpy(part, t_part, np * sizeof(int), hipMemcpyDeviceToHost));
+    if (nearest) HIP_TRY(hipMemcpy(nearest, t_near, np * 3 * sizeof(T), hipMemcpyDeviceToHost));
+    return MOSHII_OK;
+}
+
+// The meshes exist only in the handle's scratch, a batch of frames at a time, sized and exported as moshii_virtual_markers_* does;
+// each batch's points meet their own frames' meshes there and only the F x N results leave.
+template <class T>
+static int marker_surface_distance_impl(moshii_model_t m, int32_t F, const T* pose, const T* trans, const T* shape, int32_t N, const T* points,
+                                        T* dist, int32_t* face, int32_t* part, T* nearest, uint32_t flags, void* stream_, const char* name) {
+    if (const char* bad = sd_check(m, F, N, dist)) return fail(MOSHII_ERR_ARG, std::string(name) + ": " + bad);
+    if (shape && m->nshape == 0) return fail(MOSHII_ERR_ARG, "shape coefficients without a block: call moshii_model_set_free_shape first");
+    if (!m->d_sd_tris) return fail(MOSHII_ERR_ARG, std::string(name) + ": the model has no faces: call moshii_model_set_faces first");
+    if (F == 0 || N == 0) return MOSHII_OK;
+    if (!pose || !trans || !points) return fail(MOSHII_ERR_ARG, std::string(name) + ": pose, trans or points is null");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (sizeof(T) == 4 && !m->l32_valid) { int rc = moshii_lbs32_prepare(m); if (rc) return rc; }
+    const bool dev = (flags & MOSHII_BUFFERS_DEVICE) != 0;
+    const size_t frame_bytes = (size_t)m->V * 3 * sizeof(T);
+    long long batch = std::max<long long>(1, (long long)((size_t)256 << 20) / (long long)frame_bytes);
+    if (batch >= 128) batch = batch / 128 * 128;
+    if (const char* es = getenv("MOSHII_VM_BATCH")) batch = std::max(1, atoi(es));   // (tests: batch boundaries with few frames)
+    batch = std::min<long long>(std::min<long long>(batch, F), 0x7fffffffLL / N);
+    if (sizeof(T) == 8) batch = std::min<long long>(batch, 65535);   // (the f64 export puts the frames on grid.y)
+    const size_t off_win = ((size_t)batch * frame_bytes + 15) & ~(size_t)15;
+    int rc = m->vmscratch.reserve(off_win + (face ? 0 : (size_t)batch * N * sizeof(int)));   // (waits for the call before this one)
+    if (rc) return rc;
+    T* d_mesh = reinterpret_cast<T*>(m->vmscratch.ptr);
+    int* d_win = face ? (int*)nullptr : reinterpret_cast<int*>(m->vmscratch.ptr + off_win);
+    const T *d_pose = pose, *d_trans = trans, *d_shape = shape, *d_points = points;
+    T *d_dist = dist, *d_near = nearest;
+    int *d_face = face, *d_part = part;
+    T *t_pose = nullptr, *t_trans = nullptr, *t_shape = nullptr, *t_points = nullptr, *t_dist = nullptr, *t_near = nullptr;
+    int *t_face = nullptr, *t_part = nullptr;
+    const size_t np = (size_t)F * N;
+    DevTemps temps;
+    if (!dev) {
+        rc = dev_upload(pose, (size_t)F * m->NP, &t_pose); temps.keep(t_pose);
+        if (rc) return rc;
+        rc = dev_upload(trans, (size_t)F * 3, &t_trans); temps.keep(t_trans);
+        if (rc) return rc;
+        if (shape) { rc = dev_upload(shape, (size_t)F * m->nshape, &t_shape); temps.keep(t_shape); if (rc) return rc; }
+        rc = dev_upload(points, np * 3, &t_points); temps.keep(t_points);
+        if (rc) return rc;
+        HIP_TRY(hipMalloc((void**)&t_dist, np * sizeof(T))); temps.keep(t_dist);
+        if (face) { HIP_TRY(hipMalloc((void**)&t_face, np * sizeof(int))); temps.keep(t_face); }
+        if (part) { HIP_TRY(hipMalloc((void**)&t_part, np * sizeof(int))); temps.keep(t_part); }
+        if (nearest) { HIP_TRY(hipMalloc((void**)&t_near, np * 3 * sizeof(T))); temps.keep(t_near); }
+        d_pose = t_pose; d_trans = t_trans; d_points = t_points; d_dist = t_dist; d_face = t_face; d_part = t_part; d_near = t_near;
+        if (shape) d_shape = t_shape;
+    }
+    m->vmscratch.used = true; m->vmscratch.last_stream = stream;
+    for (long long f0 = 0; f0 < F; f0 += batch) {
+        const int nf = (int)std::min<long long>(batch, F - f0);
+        const size_t at = (size_t)f0 * N;
+        HIP_TRY(export_batch(m, nf, d_pose + (size_t)f0 * m->NP, d_trans + (size_t)f0 * 3,
+                             d_shape ? d_shape + (size_t)f0 * m->nshape : (const T*)nullptr, d_mesh, stream));
+        rc = surface_distance_launch(m, nf, (const T*)d_mesh, N, d_points + at * 3, d_dist + at, d_face ? d_face + at : (int*)nullptr,
+                                     d_part ? d_part + at : (int*)nullptr, d_near ? d_near + at * 3 : (T*)nullptr, d_win, stream);
+        if (rc) return rc;
+    }
+    if (!dev) {
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemcpy(dist, t_dist, np * sizeof(T), hipMemcpyDeviceToHost));
+        if (face) HIP_TRY(hipMemcpy(face, t_face, np * sizeof(int), hipMemcpyDeviceToHost));
+        if (part) HIP_TRY(hipMemcpy(part, t_part, np * sizeof(int), hipMemcpyDeviceToHost));
+        if (nearest) HIP_TRY(hipMemcpy(nearest, t_near, np * 3 * sizeof(T), hipMemcpyDeviceToHost));
+    }
+    return MOSHII_OK;
+}
+
+extern "C" {
+
+int moshii_surface_distance_f32(moshii_model_t m, int32_t F, const float* verts, int32_t N, const float* points, float* dist, int32_t* face,
+                                int32_t* part, float* nearest, uint32_t flags, void* stream) {
+    return surface_distance_impl(m, F, verts, N, points, dist, face, part, nearest, flags, stream, "moshii_surface_distance_f32");
+}
+int moshii_surface_distance_f64(moshii_model_t m, int32_t F, const double* verts, int32_t N, const double* points, double* dist, int32_t* face,
+                                int32_t* part, double* nearest, uint32_t flags, void* stream) {
+    return surface_distance_impl(m, F, verts, N, points, dist, face, part, nearest, flags, stream, "moshii_surface_distance_f64");
+}
+int moshii_marker_surface_distance_f32(moshii_model_t m, int32_t F, const float* pose, const float* trans, const float* shape, int32_t N,
+                                       const float* points, float* dist, int32_t* face, int32_t* part, float* nearest, uint32_t flags, void* stream) {
+    return marker_surface_distance_impl(m, F, pose, trans, shape, N, points, dist, face, part, nearest, flags, stream, "moshii_marker_surface_distance_f32");
+}
+int moshii_marker_surface_distance_f64(moshii_model_t m, int32_t F, const double* pose, const double* trans, const double* shape, int32_t N,
+                                       const double* points, double* dist, int32_t* face, int32_t* part, double* nearest, uint32_t flags, void* stream) {
+    return marker_surface_distance_impl(m, F, pose, trans, shape, N, points, dist, face, part, nearest, flags, stream, "moshii_marker_surface_distance_f64");
 }
 
 int moshii_prior_create(int32_t G, int32_t npose, const double* means, const double* chols, const double* weights,

@@ -500,3 +500,56 @@ def stageii_virtual_markers(stageii_data_or_fname, marker_layout, surface_model=
         else:
             np.savez(_makepath(str(out_fname)), markers=markers, labels=labels, frame_rate=rate)
     return dict(markers=markers, labels=labels, vids=vids, m2b=m2b)
+
+
+def _stageii_marker_skin_distance_plan(pkl, surface_model, frame_ids):
+    """Every refusal of stageii_marker_skin_distance that needs no model file and no device; (plan, labels, points[T, M, 3])."""
+    plan = _stageii_vertices_plan(pkl, frame_ids)
+    dbg = pkl['stageii_debug_details']
+    src = dbg if 'markers_obs' in dbg else pkl          # (load_as_amass_npz(include_markers=True) lifts them to the top level)
+    for k in ('markers_obs', 'labels_obs'):
+        if k not in src:
+            raise KeyError(f"stageii_marker_skin_distance: the Stage-II data has no '{k}'")
+    T = np.asarray(pkl['fullpose']).shape[0]
+    if len(src['markers_obs']) != T or len(src['labels_obs']) != T:
+        raise ValueError(f"stageii_marker_skin_distance: markers_obs / labels_obs hold {len(src['markers_obs'])} / {len(src['labels_obs'])} "
+                         f"frames, the result {T}")
+    if surface_model is not None and getattr(surface_model, 'f', None) is None:
+        raise ValueError('stageii_marker_skin_distance: the surface model has no faces (f)')
+    if 'latent_labels' in pkl:
+        labels = list(pkl['latent_labels'])
+    else:                                                # the labels in the order the frames first name them
+        labels = list(dict.fromkeys(l for row in src['labels_obs'] for l in row))
+    from .chmosh import pack_observed_markers
+    try:
+        points = pack_observed_markers(src['markers_obs'], src['labels_obs'], labels, plan[5])
+    except ValueError as e:
+        raise ValueError(f'stageii_marker_skin_distance: {e}') from None
+    return plan, labels, points
+
+
+def stageii_marker_skin_distance(stageii_data_or_fname, surface_model=None, frame_ids=None, dtype=np.float32):
+    """How far from the solved skin every observed marker sits, on every frame, and on which side -- the reference's
+    PtsToMesh(signed=True) (scan2mesh/mesh_distance_main.py:158-297) between the markers_obs a Stage-II result stores and the meshes
+    it describes (pose, translation, betas and per-frame expression / DMPL coefficients as in stageii_vertices); the meshes stay on the
+    device.  Markers that sank into the body, swapped labels, a layout whose distance from the skin does not fit the subject and
+    frames where the fit drifts all show here.
+
+    Returns dict(labels, distance[T, M] signed metres (NaN where a label is not observed on a frame), face[T, M], part[T, M]
+    (0 interior, 1-3 edges, 4-6 vertices; -1 unobserved), frame_ids, summary): summary[label] = dict(count, median, p5, p95,
+    negative_share) over the label's observed frames.  surface_model / frame_ids / dtype: as in stageii_vertices."""
+    pkl = _stageii_load(stageii_data_or_fname)
+    plan, labels, points = _stageii_marker_skin_distance_plan(pkl, surface_model, frame_ids)
+    sm, mp, kind, start, count, ids = plan
+    surface_model, shapedirs, b, fullpose, trans, coef = _stageii_export_inputs(pkl, plan, surface_model)
+    if getattr(surface_model, 'f', None) is None:
+        raise ValueError('stageii_marker_skin_distance: the surface model has no faces (f)')
+    dev = _stageii_device(surface_model, shapedirs, b, kind, start, count)
+    try:
+        dev.set_faces(surface_model.f)
+        res = dev.marker_surface_distance(fullpose, trans, points, shape=coef, dtype=dtype)
+    finally:
+        dev.close()
+    from .chmosh import skin_distance_summary
+    return dict(labels=labels, distance=res.distance, face=res.face, part=res.part, frame_ids=np.asarray(ids),
+                summary=skin_distance_summary(res.distance, labels))

@@ -5,7 +5,10 @@ extra shapedirs columns (a unit coefficient moves a vertex by up to 1 cm), the c
 --normals [F] [reps] [--model NAME]: vertex normals and virtual markers of exported meshes on the triangulated synthetic body of the
 family (synth.synth_mesh_model, seed 1000; default smplh, 4000 frames): the export alone, the normals alone through the LDS kernel
 and through the gather kernel, export + normals, and the virtual-marker call for 53 markers -- HIP events on device buffers, us and the
-fraction of 8 TB/s under F V 24 B + the face table."""
+fraction of 8 TB/s under F V 24 B + the face table.
+--surface-distance [F] [reps] [--model NAME]: the signed marker-to-skin distance of 53 points a frame on the same body: the staged f32
+kernel, the gather kernel in f32 and f64, and the fused entry (export + distance, meshes in the handle's scratch) -- ms, point-triangle
+tests per second and the share of the f32 vector peak the tests' arithmetic comes to."""
 import ctypes as C, sys, time
 import numpy as np
 sys.path.insert(0, '.')
@@ -86,6 +89,108 @@ def normals_bench(argv):
     print(f'  check: device-buffer normals vs the host-buffer call on 2 frames: max |diff| {np.abs(normals[:2].cpu().numpy() - ref).max():.1e}')
 
 
+def surface_distance_bench(argv):
+    import os
+    import torch
+    from moshpp_amd import synth, workload
+    mt = 'smplh'
+    if '--model' in argv:
+        i = argv.index('--model')
+        mt = argv[i + 1]
+        del argv[i:i + 2]
+    F = int(argv[0]) if len(argv) > 0 else 4000
+    reps = int(argv[1]) if len(argv) > 1 else 5
+    N = 53
+    dd = synth.synth_mesh_model(mt, seed=1000)
+    job = workload.make_job(mt, 8, {'smplh': 53, 'smpl': 41, 'smplx': 89, 'mano': 33}[mt], seed=1000, optimize_fingers=(mt == 'mano'), dd=dd)
+    solver = workload.make_solver(job)
+    model, sm = solver.dev, job['sm']
+    faces = np.asarray(dd['f'], dtype=np.int32)
+    model.set_faces(faces)
+    V, NF = sm.V, len(faces)
+    dev = torch.device('cuda', 0)
+    rng = np.random.default_rng(0)
+    pose = torch.from_numpy(rng.normal(0, 0.3, (F, sm.NP)).astype(np.float32)).to(dev)
+    trans = torch.from_numpy(rng.normal(0, 1, (F, 3)).astype(np.float32)).to(dev)
+    verts = torch.empty((F, V, 3), dtype=torch.float32, device=dev)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    model.lbs_forward_device(F, pose.data_ptr(), trans.data_ptr(), verts.data_ptr(), stream)
+    torch.cuda.synchronize()
+    # the points: markers about a centimetre off the skin -- 53 vertices of each frame, moved by up to 1.5 cm
+    vids = torch.from_numpy(rng.choice(V, N, replace=False)).to(dev)
+    points = (verts[:, vids] + torch.from_numpy(rng.uniform(-0.015, 0.015, (F, N, 3)).astype(np.float32)).to(dev)).contiguous()
+    dist = torch.empty((F, N), dtype=torch.float32, device=dev)
+    face = torch.empty((F, N), dtype=torch.int32, device=dev)
+    part = torch.empty((F, N), dtype=torch.int32, device=dev)
+    near = torch.empty((F, N, 3), dtype=torch.float32, device=dev)
+    F64 = min(F, 1000)                            # (the f64 leg on fewer frames: it is the slow one)
+    verts64, points64 = verts[:F64].double(), points[:F64].double()
+    dist64 = torch.empty((F64, N), dtype=torch.float64, device=dev)
+    near64 = torch.empty((F64, N, 3), dtype=torch.float64, device=dev)
+    plain = lambda: model.surface_distance_device(F, verts.data_ptr(), N, points.data_ptr(), dist.data_ptr(), face.data_ptr(), part.data_ptr(),
+                                                  near.data_ptr(), stream)
+    plain64 = lambda: model.surface_distance_device(F64, verts64.data_ptr(), N, points64.data_ptr(), dist64.data_ptr(), face.data_ptr(),
+                                                    part.data_ptr(), near64.data_ptr(), stream, f32=False)
+    fused = lambda: model.marker_surface_distance_device(F, pose.data_ptr(), trans.data_ptr(), N, points.data_ptr(), dist.data_ptr(),
+                                                         face.data_ptr(), part.data_ptr(), near.data_ptr(), stream)
+    export = lambda: model.lbs_forward_device(F, pose.data_ptr(), trans.data_ptr(), verts.data_ptr(), stream)
+
+    def timed(fn):
+        for _ in range(2):
+            fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(3):              # three rounds: the spread
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) * 1e-3 / reps)
+        return min(ts), max(ts)
+
+    OPS = 75                                      # f32 operations of one point-triangle test in sd_search (fma = 2), counted from the source
+    print(f'{mt} mesh body: V = {V}, {NF} faces, F = {F} frames x {N} points = {F * N * NF / 1e9:.2f} G point-triangle tests, {reps} calls a round, '
+          f'3 rounds (fastest .. slowest round); library {os.path.basename(capi.LIB_PATH)} {capi.load().moshii_source_hash().decode()}')
+
+    def line(name, lo, hi, frames, peak=True):
+        tests = frames * N * NF
+        extra = f'   {tests * OPS / lo / 157.3e12 * 100:5.1f} % of the 157.3 TFLOPS f32 vector peak at {OPS} flop a test' if peak else ''
+        print(f'  {name:38s} {lo * 1e3:9.3f} .. {hi * 1e3:9.3f} ms   {tests / lo / 1e9:8.1f} G tests/s{extra}')
+
+    os.environ['MOSHII_SD_KERNEL'] = 'lds'
+    lo, hi = timed(plain)
+    del os.environ['MOSHII_SD_KERNEL']
+    kname, klds, kthreads = capi.last_launch_info()
+    assert kname == 'k_sd_lds', kname
+    line('staged f32 kernel (k_sd_lds)', lo, hi, F)
+    print(f'  ({kname}: {klds} B of LDS a workgroup, {kthreads} threads)')
+    staged = dist.clone()
+    lo_g, hi_g = timed(plain)
+    assert capi.last_launch_info()[0] == 'k_sd_gather<float>', capi.last_launch_info()
+    line('gather f32 kernel (the default)', lo_g, hi_g, F)
+    same = bool((staged == dist).all() | (torch.isnan(staged) & torch.isnan(dist)).all())
+    print(f'  (the two f32 kernels agree bit for bit: {same}; staged / gather time {lo / lo_g:.2f})')
+    lo, hi = timed(plain64)
+    assert capi.last_launch_info()[0] == 'k_sd_gather<double>', capi.last_launch_info()
+    line(f'gather f64 kernel ({F64} frames)', lo, hi, F64, peak=False)
+    lo, hi = timed(export)
+    print(f'  {"export alone":38s} {lo * 1e3:9.3f} .. {hi * 1e3:9.3f} ms')
+    lo, hi = timed(fused)
+    line('fused entry (export + distance, default)', lo, hi, F, peak=False)
+    ref = model.surface_distance(verts[:2].cpu().numpy(), points[:2].cpu().numpy())
+    plain()
+    torch.cuda.synchronize()
+    print(f'  check: device-buffer distances vs the host-buffer call on 2 frames: max |diff| {np.abs(dist[:2].cpu().numpy() - ref.distance).max():.1e}; '
+          f'|d| median {float(dist.abs().median()) * 1e3:.2f} mm, {float((dist < 0).float().mean()) * 100:.1f} % inside')
+
+
+if '--surface-distance' in sys.argv:
+    from moshpp_amd import capi
+    sys.argv.remove('--surface-distance')
+    surface_distance_bench(sys.argv[1:])
+    sys.exit(0)
 if '--normals' in sys.argv:
     from moshpp_amd import capi
     sys.argv.remove('--normals')

@@ -11,6 +11,7 @@
 // (fewer fibers per workgroup: the kernels are correct for any power of two >= 64 / >= 1, the summation order follows them).
 #include <hip/hip_runtime.h>
 #include "stagei_views.h"
+#include "stagei_plan.h"
 #include "../../include/moshii.h"
 #include <math.h>
 #include <stdio.h>
@@ -1381,6 +1382,8 @@ KERNEL k_s1_back(const int* fcols, int fs, const int* scols, int ns, int nsp, co
 // ---------------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------------
+namespace sp = stagei_plan;
+using sp::Vec;
 
 struct DevPool {        // every device allocation of one solve; freed together
     std::vector<void*> ptrs;
@@ -1399,256 +1402,327 @@ struct DevPool {        // every device allocation of one solve; freed together
     ~DevPool() { for (void* q : ptrs) hipFree(q); }
 };
 
-static double nrm2(const std::vector<double>& v) { double s = 0; for (double x : v) s += x * x; return sqrt(s); }
-static double dotv(const std::vector<double>& a, const std::vector<double>& b) { double s = 0; for (size_t i = 0; i < a.size(); ++i) s += a[i] * b[i]; return s; }
-
-}  // namespace
-
-// One Stage-I solve.  `mv` / `pv`: device views of the model / prior (moshii_api.hip fills them from the handles).
-int moshii_stagei_core(const S1ModelView* mv, const S1PriorView* pv, const moshii_stagei_desc* ds, void* stream_, char* err, int errlen) {
-    hipStream_t st = (hipStream_t)stream_;
-    auto fail = [&](int code, const char* msg) { snprintf(err, errlen, "%s", msg); return code; };
-    S1Dims d; memset(&d, 0, sizeof(d));
-    S1Ptr p; memset(&p, 0, sizeof(p));
-    d.F = ds->n_frames; d.M = ds->M; d.NPZ = d.F + 1;
-    d.per_frame = ds->n_expr > 0 ? 1 : 0;
-    d.nb = d.per_frame ? ds->n_expr : ds->nb; d.shape_start = d.per_frame ? ds->expr_start : 0;
-    if (d.per_frame && ds->nb != 0) return fail(MOSHII_ERR_ARG, "stagei: free expressions need fixed betas (nb = 0; chmosh.py:295-299)");
-    d.V = mv->V; d.K = mv->K; d.P = 3 * mv->K; d.NP = mv->NP; d.body_dof = mv->body_dof; d.hand_dof = mv->hand_dof;
-    d.nhand_full = d.P - d.body_dof; d.NBtot = mv->NB; d.nfeat = 9 * (mv->K - 1);
-    d.nfaces = ds->n_faces; d.nbody = ds->n_body; d.G = pv ? pv->G : 0; d.npose_prior = pv ? pv->npose : 0;
-    d.ncan = 9 * d.M;
-    if (d.F < 1 || d.M < 3 || d.nb < 0 || d.shape_start < 0 || d.shape_start + d.nb > d.NBtot) return fail(MOSHII_ERR_ARG, "stagei: bad sizes");
-    if (pv && d.nbody != pv->npose) return fail(MOSHII_ERR_ARG, "stagei: prior size != number of body pose ids");
-    if (d.G > 64) return fail(MOSHII_ERR_ARG, "stagei: more than 64 mixture components");
-    const int F = d.F, M = d.M, nb = d.nb, NP = d.NP, K = d.K;
-    int ntot_obs = 0;
-    std::vector<int> obs_off(F + 1, 0);
-    for (int f = 0; f < F; ++f) {
-        if (ds->n_obs[f] < 3) return fail(MOSHII_ERR_ARG, "stagei: a picked frame has fewer than 3 observed layout markers (no rigid start possible)");
-        ntot_obs += ds->n_obs[f]; obs_off[f + 1] = ntot_obs;
+// The blocked Cholesky factorisation of A (n x n, in place; dinv: the panels' inverse diagonal blocks; status[1]: a pivot was not positive)
+void s1_chol_factor(double* A, int n, double* dinv, int* status, hipStream_t st) {
+    for (int j0 = 0; j0 < n; j0 += S1_PB) {
+        const int jb = std::min(S1_PB, n - j0), rem = n - j0 - jb;
+        LAUNCH(k_s1_chol_diag, 1, 1, S1_TRSM_TPB, st, A, n, j0, dinv, status);
+        if (rem > 0) LAUNCH(k_s1_chol_trsm, (rem + S1_TRSM_TPB - 1) / S1_TRSM_TPB, 1, S1_TRSM_TPB, st, A, n, j0, dinv);
+        if (rem > 0) { int nt = (rem + S1_PB - 1) / S1_PB; LAUNCH(k_s1_chol_update, nt, nt, 256, st, A, n, j0, jb); }
     }
-    for (int i = 0; i < ntot_obs; ++i) if (ds->obs_ids[i] < 0 || ds->obs_ids[i] >= M) return fail(MOSHII_ERR_ARG, "stagei: observed marker id out of range");
+}
 
-    // frames of this rank (moshii_stagei_desc.sharded): every rank evaluates the canonical body and the attachment, the data / prior /
-    // finger rows of its own frames, one rank the shared rows; normal equations and SSE are summed over the ranks through the
-    // caller's all-reduce, after which every rank holds the same system and takes the same step
-    const bool shard = ds->sharded && ds->allreduce_sum;
-    const int f_lo = shard ? ds->frame_lo : 0, f_hi = shard ? ds->frame_hi : F, nown = f_hi - f_lo;
-    const int own_shared = shard ? (ds->owns_shared_rows ? 1 : 0) : 1;
-    // (a rank whose arguments are wrong must not just return: the others would wait in the first all-reduce.  Its verdict is summed
-    //  over the ranks below, as soon as reduce() exists, and every rank fails together.)
-    const bool bad_range = shard && (f_lo < 0 || f_hi > F || nown < 0);
-    // the arrow solver back-substitutes the shared block on a rank with frames (the dense solver, MOSHII_S1_SOLVER=dense, has no such need)
-    const char* solver_env0 = getenv("MOSHII_S1_SOLVER");
-    const bool bad_owner = shard && own_shared && nown <= 0 && !(solver_env0 && strcmp(solver_env0, "dense") == 0);
-    int reduce_rc = 0;
-    DevPool pool;
-    // sums over the ranks.  reduce(): a host vector; reduce_dev(): one of the solver's device buffers.  With allreduce_on_device the
-    // callback works on device memory (RCCL): device buffers are summed in place, host vectors are staged through d_red; without it
-    // the callback works on host memory (gloo, or nccl behind a copy) and device buffers take the round trip through `hred`.
-    const bool red_dev = shard && ds->allreduce_on_device;
-    double* d_red = nullptr; long long d_red_cap = 0;
-    std::vector<double> hred;
-    auto reduce = [&](double* buf, long long count) {
-        if (!shard || count <= 0) return;
-        if (!red_dev) { if (ds->allreduce_sum(buf, count, ds->allreduce_user) != 0) reduce_rc = 1; return; }
-        if (count > d_red_cap) { d_red = pool.get<double>((size_t)count); d_red_cap = count; if (!pool.ok) { reduce_rc = 1; return; } }
+// The arrow-structured Gauss-Newton step on the frames [f_lo, f_lo + nown) of F: per-frame elimination + Schur complement on the shared
+// block.  A: n x n (lower part read), g: n, fcols: F x fs, scols: ns, ones: all-ones SYRK flags; Linv F x fs x fs, Y F x fs x nsp,
+// z F x fs, T / S ns x ns, h / ds ns, dinv as s1_chol_factor.
+struct S1Arrow {
+    const double* A; int n; const double* g; const int* fcols; int F, fs; const int* scols; int ns, nsp; const int* ones;
+    double *Linv, *Y, *z, *T, *S, *h, *dinv, *ds; int* status; int f_lo, nown;
+};
+// first half: eliminate + SYRK + Schur subtraction -> S, h (what a sharded solve sums over the ranks)
+void s1_arrow_reduce(const S1Arrow& a, hipStream_t st) {
+    const size_t lds_bytes = ((size_t)a.fs * (a.fs + 1) + 2 * (size_t)a.fs) * sizeof(double);
+    hipMemsetAsync(a.Y, 0, (size_t)a.F * a.fs * a.nsp * 8, st);
+    hipMemsetAsync(a.z, 0, (size_t)a.F * a.fs * 8, st);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k_s1_elim), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    // (sharded: every rank eliminates its own frames -- their rows live only here, so A_ff, A_fs and g_f are complete --
+    //  and contributes A_ss,r - Y_r^T Y_r and g_s,r - Y_r^T z_r; the sum over ranks is the Schur system: ns^2 + ns doubles)
+    if (a.nown > 0) LAUNCH_LDS(k_s1_elim, a.nown, 1, S1_TPB, lds_bytes, st, a.A, a.n, a.g, a.fcols, a.fs, a.scols, a.ns, a.nsp, a.Linv, a.Y, a.z, a.status, a.f_lo);
+    if (a.nown > 0) {
+        const size_t ybytes = ((size_t)a.fs * (a.fs + 1) + (size_t)S1_YC * a.fs) * sizeof(double);
+        hipFuncSetAttribute(reinterpret_cast<const void*>(k_s1_elim_y), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ybytes);
+        LAUNCH_LDS(k_s1_elim_y, a.nown, (a.ns + 1 + S1_YC - 1) / S1_YC, S1_TPB, ybytes, st, a.A, a.n, a.g, a.fcols, a.fs, a.scols, a.ns, a.nsp, a.Linv, a.Y, a.z, a.f_lo);
+    }
+    { int nt = (a.ns + S1_T - 1) / S1_T; LAUNCH(k_s1_syrk, nt, nt, 256, st, a.Y, a.F * a.fs, a.ns, a.nsp, a.T, a.ones); }
+    LAUNCH(k_s1_schur_sub, a.ns, 1, S1_TPB, st, a.A, a.n, a.g, a.scols, a.ns, a.T, a.Y, a.nsp, a.z, a.F * a.fs, a.S, a.h);
+}
+// second half: factor S, ds = S^-1 h, back-substitution of the frames' blocks into out (n; cleared first if clear_out)
+void s1_arrow_solve(const S1Arrow& a, double* out, bool clear_out, int scatter_shared, hipStream_t st) {
+    s1_chol_factor(a.S, a.ns, a.dinv, a.status, st);
+    LAUNCH(k_s1_tri_solve, 1, 1, S1_CHOL_TPB, st, a.S, a.ns, a.dinv, a.h, a.ds);
+    if (clear_out) hipMemsetAsync(out, 0, (size_t)a.n * 8, st);
+    if (a.nown > 0) LAUNCH(k_s1_back, a.nown, 1, S1_TPB, st, a.fcols, a.fs, a.scols, a.ns, a.nsp, a.Linv, a.Y, a.z, a.ds, out, a.f_lo, scatter_shared);
+}
+
+// Sums over the ranks of a sharded solve.  reduce(): a host vector; reduce_dev(): one of the solver's device buffers.  With
+// allreduce_on_device the callback works on device memory (RCCL): device buffers are summed in place, host vectors are staged through
+// d_red; without it the callback works on host memory (gloo, or nccl behind a copy) and device buffers take the round trip through `hred`.
+struct RankSum {
+    const moshii_stagei_desc* ds; hipStream_t st; DevPool& pool;
+    const bool on, dev;
+    int rc = 0;                 // a callback (or a staging allocation) failed
+    double* d_red = nullptr; long long cap = 0;
+    Vec hred;
+    RankSum(const moshii_stagei_desc* ds_, hipStream_t st_, DevPool& pool_)
+        : ds(ds_), st(st_), pool(pool_), on(ds_->sharded && ds_->allreduce_sum), dev(on && ds_->allreduce_on_device) {}
+    void reduce(double* buf, long long count) {
+        if (!on || count <= 0) return;
+        if (!dev) { if (ds->allreduce_sum(buf, count, ds->allreduce_user) != 0) rc = 1; return; }
+        if (count > cap) { d_red = pool.get<double>((size_t)count); cap = count; if (!pool.ok) { rc = 1; return; } }
         hipMemcpyAsync(d_red, buf, (size_t)count * 8, hipMemcpyHostToDevice, st);
         hipStreamSynchronize(st);
-        if (ds->allreduce_sum(d_red, count, ds->allreduce_user) != 0) reduce_rc = 1;
+        if (ds->allreduce_sum(d_red, count, ds->allreduce_user) != 0) rc = 1;
         hipMemcpyAsync(buf, d_red, (size_t)count * 8, hipMemcpyDeviceToHost, st);
         hipStreamSynchronize(st);
-    };
-    auto reduce_dev = [&](double* dbuf, long long count) {
-        if (!shard || count <= 0) return;
+    }
+    void reduce_dev(double* dbuf, long long count) {
+        if (!on || count <= 0) return;
         hipStreamSynchronize(st);
-        if (red_dev) { if (ds->allreduce_sum(dbuf, count, ds->allreduce_user) != 0) reduce_rc = 1; return; }
+        if (dev) { if (ds->allreduce_sum(dbuf, count, ds->allreduce_user) != 0) rc = 1; return; }
         hred.resize((size_t)count);
         hipMemcpyAsync(hred.data(), dbuf, (size_t)count * 8, hipMemcpyDeviceToHost, st);
         hipStreamSynchronize(st);
-        if (ds->allreduce_sum(hred.data(), count, ds->allreduce_user) != 0) reduce_rc = 1;
+        if (ds->allreduce_sum(hred.data(), count, ds->allreduce_user) != 0) rc = 1;
         hipMemcpyAsync(dbuf, hred.data(), (size_t)count * 8, hipMemcpyHostToDevice, st);
         hipStreamSynchronize(st);
-    };
-    if (shard) {
+    }
+    // A rank whose arguments are wrong must not just return: the others would wait in the first all-reduce.  Its verdict is summed
+    // over the ranks here and every rank fails together.  Returns 0 or the error code, *msg set.
+    int verdict(bool bad_range, bool bad_owner, long long cap0, const char** msg) {
+        if (!on) return 0;
         // The device path stages host vectors through d_red: that buffer is sized HERE, before the first collective, for the largest
         // vector the solve will ever stage (the n unknowns; 3 F M marker coordinates), so that no rank can drop out of a LATER all-reduce
         // because of it.  A rank that does not get it still joins the verdict sum -- through a 32-byte buffer -- and reports the failure
         // there, so that ALL ranks fail together instead of the others waiting in their first all-reduce for the process group's
         // timeout; only a rank that cannot even get those 32 bytes fails alone.
-        double verdict[3] = {bad_range ? 1.0 : 0.0, bad_owner ? 1.0 : 0.0, 0.0};
-        if (red_dev) {
-            const long long cap0 = 3LL * M + (long long)F * (3 + NP) + (long long)nb * (d.per_frame ? F : 1) + 3LL * F * M + 6LL * F + 64;   // >= n, 3 F M, 6 F
+        double v[3] = {bad_range ? 1.0 : 0.0, bad_owner ? 1.0 : 0.0, 0.0};
+        if (dev) {
             d_red = pool.get<double>((size_t)cap0);
-            d_red_cap = pool.ok ? cap0 : 0;
+            cap = pool.ok ? cap0 : 0;
             if (!pool.ok) {
-                verdict[2] = 1.0;
+                v[2] = 1.0;
                 double* tiny = nullptr;
-                if (hipMalloc((void**)&tiny, 4 * sizeof(double)) != hipSuccess)
-                    return fail(MOSHII_ERR_HIP, "stagei: device allocation failed before the first all-reduce (the other ranks were not joined)");
-                d_red = tiny; d_red_cap = 4;
-                reduce(verdict, 3);
+                *msg = "stagei: device allocation failed before the first all-reduce (the other ranks were not joined)";
+                if (hipMalloc((void**)&tiny, 4 * sizeof(double)) != hipSuccess) return MOSHII_ERR_HIP;
+                d_red = tiny; cap = 4;
+                reduce(v, 3);
                 hipFree(tiny);
-                return fail(MOSHII_ERR_HIP, "stagei: device allocation of the all-reduce staging buffer failed on this rank (all ranks were told)");
+                *msg = "stagei: device allocation of the all-reduce staging buffer failed on this rank (all ranks were told)";
+                return MOSHII_ERR_HIP;
             }
         }
-        reduce(verdict, 3);
-        if (reduce_rc) return fail(MOSHII_ERR_ARG, "stagei: the all-reduce callback failed");
-        if (verdict[2] > 0) return fail(MOSHII_ERR_HIP, "stagei: device allocation of the all-reduce staging buffer failed on another rank");
-        if (verdict[0] > 0) return fail(MOSHII_ERR_ARG, "stagei: frame range of a rank out of bounds");
-        if (verdict[1] > 0) return fail(MOSHII_ERR_ARG, "stagei: the rank that owns the shared rows must own at least one frame");
+        reduce(v, 3);
+        if (rc) { *msg = "stagei: the all-reduce callback failed"; return MOSHII_ERR_ARG; }
+        if (v[2] > 0) { *msg = "stagei: device allocation of the all-reduce staging buffer failed on another rank"; return MOSHII_ERR_HIP; }
+        if (v[0] > 0) { *msg = "stagei: frame range of a rank out of bounds"; return MOSHII_ERR_ARG; }
+        if (v[1] > 0) { *msg = "stagei: the rank that owns the shared rows must own at least one frame"; return MOSHII_ERR_ARG; }
+        return 0;
     }
-    // ---- constants
-    p.parents = mv->parents; p.vt = mv->vt; p.shapedirs = mv->shapedirs; p.posedirs = mv->posedirs; p.weights = mv->weights;
-    p.Jreg = mv->Jreg; p.hands_mean = mv->hands_mean; p.comps = mv->comps; p.anc = mv->anc;
-    if (pv) { p.means = pv->means; p.chols = pv->chols; p.neglogw = pv->neglogw; }
-    p.faces = pool.put(ds->faces, (size_t)3 * d.nfaces, st);
-    {   // vertex -> incident faces
-        std::vector<int> ptr(d.V + 1, 0), lst((size_t)3 * d.nfaces);
-        for (int i = 0; i < 3 * d.nfaces; ++i) {
-            if (ds->faces[i] < 0 || ds->faces[i] >= d.V) return fail(MOSHII_ERR_ARG, "stagei: face index out of range");
-            ptr[ds->faces[i] + 1]++;
+};
+
+// One Stage-I solve: the steps of moshii_stagei_core over one state.  It is also the dogleg's problem (eval / normal_eq / Ax / gn_step).
+struct S1Solve {
+    const S1ModelView* mv; const S1PriorView* pv; const moshii_stagei_desc* ds; hipStream_t st; char* err; int errlen;
+    S1Dims d; S1Ptr p;
+    DevPool pool; RankSum sum;
+    // frames of this rank (moshii_stagei_desc.sharded): every rank evaluates the canonical body and the attachment, the data / prior /
+    // finger rows of its own frames, one rank the shared rows; normal equations and SSE are summed over the ranks through the
+    // caller's all-reduce, after which every rank holds the same system and takes the same step
+    bool shard = false, bad_range = false, bad_owner = false, want_schur = true;
+    int f_lo = 0, f_hi = 0, nown = 0, own_shared = 1, ntot_obs = 0, nface_all = 0;
+    std::vector<int> obs_off, v2f_ptr, v2f;       // observation offsets per frame; vertex -> incident faces
+    sp::Facts k; sp::Layout lay, mx;              // the current evaluation and its layout; the largest layout of the rounds
+    // the round: pose columns, solver, which rows the evaluation has
+    sp::PoseCols pc; bool rigid = false, schur = false, no_prior = false, rows_on = true;
+    // device work buffers
+    int *d_colmap = nullptr, *d_finger = nullptr, *d_fcols = nullptr, *d_scols = nullptr, *d_ones = nullptr, *d_flags = nullptr;
+    double *d_point = nullptr, *d_A = nullptr, *d_L = nullptr, *d_Linv = nullptr, *d_Y = nullptr, *d_z = nullptr, *d_T = nullptr, *d_S = nullptr,
+           *d_h = nullptr, *d_ds = nullptr, *d_dinv = nullptr, *d_g = nullptr, *d_part = nullptr, *d_vec = nullptr, *d_out = nullptr;
+    // host state: the point, its staging copy (offsets of trans | latent markers | betas in it), the residual
+    Vec pose, trans, ml, betas, hpoint, r;
+    size_t pt_o_trans = 0, pt_o_ml = 0, pt_o_betas = 0;
+    int total_iters = 0;
+
+    S1Solve(const S1ModelView* mv_, const S1PriorView* pv_, const moshii_stagei_desc* ds_, hipStream_t st_, char* err_, int errlen_)
+        : mv(mv_), pv(pv_), ds(ds_), st(st_), err(err_), errlen(errlen_), sum(ds_, st_, pool) {}
+    int fail(int code, const char* msg) { snprintf(err, errlen, "%s", msg); return code; }
+
+    // ---- the descriptor: sizes, every range check that depends on it alone, this rank's share
+    int check() {
+        memset(&d, 0, sizeof(d)); memset(&p, 0, sizeof(p));
+        d.F = ds->n_frames; d.M = ds->M; d.NPZ = d.F + 1;
+        d.per_frame = ds->n_expr > 0 ? 1 : 0;
+        d.nb = d.per_frame ? ds->n_expr : ds->nb; d.shape_start = d.per_frame ? ds->expr_start : 0;
+        if (d.per_frame && ds->nb != 0) return fail(MOSHII_ERR_ARG, "stagei: free expressions need fixed betas (nb = 0; chmosh.py:295-299)");
+        d.V = mv->V; d.K = mv->K; d.P = 3 * mv->K; d.NP = mv->NP; d.body_dof = mv->body_dof; d.hand_dof = mv->hand_dof;
+        d.nhand_full = d.P - d.body_dof; d.NBtot = mv->NB; d.nfeat = 9 * (mv->K - 1);
+        d.nfaces = ds->n_faces; d.nbody = ds->n_body; d.G = pv ? pv->G : 0; d.npose_prior = pv ? pv->npose : 0;
+        d.ncan = 9 * d.M;
+        if (d.F < 1 || d.M < 3 || d.nb < 0 || d.shape_start < 0 || d.shape_start + d.nb > d.NBtot) return fail(MOSHII_ERR_ARG, "stagei: bad sizes");
+        if (pv && d.nbody != pv->npose) return fail(MOSHII_ERR_ARG, "stagei: prior size != number of body pose ids");
+        if (d.G > 64) return fail(MOSHII_ERR_ARG, "stagei: more than 64 mixture components");
+        obs_off.assign(d.F + 1, 0);
+        for (int f = 0; f < d.F; ++f) {
+            if (ds->n_obs[f] < 3) return fail(MOSHII_ERR_ARG, "stagei: a picked frame has fewer than 3 observed layout markers (no rigid start possible)");
+            ntot_obs += ds->n_obs[f]; obs_off[f + 1] = ntot_obs;
         }
-        for (int v = 0; v < d.V; ++v) ptr[v + 1] += ptr[v];
-        std::vector<int> fill(ptr.begin(), ptr.end() - 1);
-        for (int f = 0; f < d.nfaces; ++f) for (int c = 0; c < 3; ++c) lst[fill[ds->faces[3 * f + c]]++] = f;
-        p.v2f_ptr = pool.put(ptr.data(), ptr.size(), st); p.v2f = pool.put(lst.data(), lst.size(), st);
+        for (int i = 0; i < ntot_obs; ++i) if (ds->obs_ids[i] < 0 || ds->obs_ids[i] >= d.M) return fail(MOSHII_ERR_ARG, "stagei: observed marker id out of range");
+        for (int i = 0; i < 3 * d.nfaces; ++i) if (ds->faces[i] < 0 || ds->faces[i] >= d.V) return fail(MOSHII_ERR_ARG, "stagei: face index out of range");
+        nface_all = d.per_frame ? ds->n_face : 0;
+        for (int i = 0; i < nface_all; ++i) if (ds->face_ids[i] < 0 || ds->face_ids[i] >= d.NP) return fail(MOSHII_ERR_ARG, "stagei: face pose id out of range");
+        d.nhead = ds->head_ids ? ds->n_head : 0; d.nhead_rows = ds->head_ids ? ds->n_head_rows : 0;
+        if (d.nhead_rows && !ds->head_corr) return fail(MOSHII_ERR_ARG, "stagei: head_ids without head_corr");
+        for (int h = 0; d.nhead_rows && h < d.nhead; ++h) if (ds->head_ids[h] < 0 || ds->head_ids[h] >= d.M) return fail(MOSHII_ERR_ARG, "stagei: head marker id out of range");
+        k = sp::Facts{d.F, d.M, ntot_obs, d.nb, d.per_frame, 0, 0, 0, 0, d.G ? d.npose_prior + 1 : 0, d.nhead_rows};
+        mx = sp::layout_max(k, ds->n_pose_ids, ds->n_finger, nface_all);          // largest problem of the rounds: all of body + fingers free
+        if (mx.n > S1_NMAX) return fail(MOSHII_ERR_ARG, "stagei: more than 4096 unknowns");
+        for (int m = 0; m < d.M; ++m) if (ds->marker_vids[m] < 0 || ds->marker_vids[m] >= d.V) return fail(MOSHII_ERR_ARG, "stagei: marker vertex id out of range");
+        for (int b = 0; b < d.nbody; ++b) if (ds->body_ids[b] < 0 || ds->body_ids[b] >= d.NP) return fail(MOSHII_ERR_ARG, "stagei: body id out of range");
+        shard = sum.on;
+        f_lo = shard ? ds->frame_lo : 0; f_hi = shard ? ds->frame_hi : d.F; nown = f_hi - f_lo;
+        own_shared = shard ? (ds->owns_shared_rows ? 1 : 0) : 1;
+        bad_range = shard && (f_lo < 0 || f_hi > d.F || nown < 0);
+        // arrow-structured solver (per-frame elimination + Schur complement on the shared block) unless MOSHII_S1_SOLVER=dense asks for
+        // the dense blocked Cholesky of the whole system.  Default since round 2: ten seeded problems (six SMPL-H seeds, fingers, SMPL-X,
+        // SMPL, fixed betas) take the same dogleg iterations with both and end within 1.3e-10 (profiles/r02_stagei_schur_seeds.txt), the
+        // arrow form 1.35-1.5x faster; sharded, it sums the 169 x 169 shared block instead of the 925 x 925 system.
+        const char* solver_env = getenv("MOSHII_S1_SOLVER");
+        want_schur = !(solver_env && strcmp(solver_env, "dense") == 0);
+        // the arrow solver back-substitutes the shared block on a rank with frames (the dense solver has no such need)
+        bad_owner = shard && own_shared && nown <= 0 && want_schur;
+        return 0;
+    }
+
+    // ---- constants of the problem: faces, vertex -> face lists, exclusion mask, observations, ids, head term
+    void upload_constants() {
+        const int M = d.M;
+        p.parents = mv->parents; p.vt = mv->vt; p.shapedirs = mv->shapedirs; p.posedirs = mv->posedirs; p.weights = mv->weights;
+        p.Jreg = mv->Jreg; p.hands_mean = mv->hands_mean; p.comps = mv->comps; p.anc = mv->anc;
+        if (pv) { p.means = pv->means; p.chols = pv->chols; p.neglogw = pv->neglogw; }
+        p.faces = pool.put(ds->faces, (size_t)3 * d.nfaces, st);
+        {   // vertex -> incident faces
+            v2f_ptr.assign(d.V + 1, 0); v2f.resize((size_t)3 * d.nfaces);
+            for (int i = 0; i < 3 * d.nfaces; ++i) v2f_ptr[ds->faces[i] + 1]++;
+            for (int v = 0; v < d.V; ++v) v2f_ptr[v + 1] += v2f_ptr[v];
+            std::vector<int> fill(v2f_ptr.begin(), v2f_ptr.end() - 1);
+            for (int f = 0; f < d.nfaces; ++f) for (int c = 0; c < 3; ++c) v2f[fill[ds->faces[3 * f + c]]++] = f;
+            p.v2f_ptr = pool.put(v2f_ptr.data(), v2f_ptr.size(), st); p.v2f = pool.put(v2f.data(), v2f.size(), st);
+            hipStreamSynchronize(st);
+        }
+        {
+            std::vector<unsigned char> ex(d.V, 0);
+            for (int i = 0; i < ds->n_exclude; ++i) if (ds->exclude_vids[i] >= 0 && ds->exclude_vids[i] < d.V) ex[ds->exclude_vids[i]] = 1;
+            p.excl = pool.put(ex.data(), ex.size(), st);
+            hipStreamSynchronize(st);
+        }
+        p.obs_ids = pool.put(ds->obs_ids, ntot_obs, st); p.obs_off = pool.put(obs_off.data(), obs_off.size(), st);
+        p.obs = pool.put(ds->obs, (size_t)3 * ntot_obs, st); p.m2b = pool.put(ds->m2b, M, st);
+        p.body_ids = pool.put(ds->body_ids, d.nbody, st);
+        p.face_ids = pool.put(ds->face_ids, nface_all, st);
+        Vec wt_init_eff(ds->wt_init, ds->wt_init + M);
+        if (d.nhead_rows) {
+            for (int h = 0; h < d.nhead; ++h) wt_init_eff[ds->head_ids[h]] = 0.0;          // the head markers leave their per-type init rows (chmosh.py:364-367)
+            p.head_ids = pool.put(ds->head_ids, d.nhead, st); p.head_C = pool.put(ds->head_corr, (size_t)d.nhead_rows * d.nhead, st);
+        }
+        p.wt_init = pool.put(wt_init_eff.data(), M, st);
         hipStreamSynchronize(st);
     }
-    {
-        std::vector<unsigned char> ex(d.V, 0);
-        for (int i = 0; i < ds->n_exclude; ++i) if (ds->exclude_vids[i] >= 0 && ds->exclude_vids[i] < d.V) ex[ds->exclude_vids[i]] = 1;
-        p.excl = pool.put(ex.data(), ex.size(), st);
-        hipStreamSynchronize(st);
-    }
-    p.obs_ids = pool.put(ds->obs_ids, ntot_obs, st); p.obs_off = pool.put(obs_off.data(), obs_off.size(), st);
-    p.obs = pool.put(ds->obs, (size_t)3 * ntot_obs, st); p.m2b = pool.put(ds->m2b, M, st);
-    p.body_ids = pool.put(ds->body_ids, d.nbody, st);
-    int* d_colmap = pool.get<int>(NP); p.colmap = d_colmap;
-    int* d_finger = pool.get<int>(std::max(1, ds->n_finger)); p.finger_ids = d_finger;
-    const int nface_all = d.per_frame ? ds->n_face : 0;
-    for (int k = 0; k < nface_all; ++k) if (ds->face_ids[k] < 0 || ds->face_ids[k] >= NP) return fail(MOSHII_ERR_ARG, "stagei: face pose id out of range");
-    p.face_ids = pool.put(ds->face_ids, nface_all, st);
-    p.cl0 = pool.get<int>(3 * M); p.coef0 = pool.get<double>(3 * M);
-    p.loss = pool.get<double>(3 * M); p.dinit = pool.get<double>((size_t)3 * M * std::max(1, nb));
-    d.nhead = ds->head_ids ? ds->n_head : 0; d.nhead_rows = ds->head_ids ? ds->n_head_rows : 0;
-    std::vector<double> wt_init_eff(ds->wt_init, ds->wt_init + M);
-    if (d.nhead_rows) {
-        if (!ds->head_corr) return fail(MOSHII_ERR_ARG, "stagei: head_ids without head_corr");
-        for (int h = 0; h < d.nhead; ++h) {
-            if (ds->head_ids[h] < 0 || ds->head_ids[h] >= M) return fail(MOSHII_ERR_ARG, "stagei: head marker id out of range");
-            wt_init_eff[ds->head_ids[h]] = 0.0;          // the head markers leave their per-type init rows (chmosh.py:364-367)
+
+    // ---- work buffers and the host point
+    int allocate() {
+        const int F = d.F, M = d.M, nb = d.nb, NP = d.NP, K = d.K, nb1 = std::max(1, nb);
+        p.colmap = d_colmap = pool.get<int>(NP); p.finger_ids = d_finger = pool.get<int>(std::max(1, ds->n_finger));
+        p.cl0 = pool.get<int>(3 * M); p.coef0 = pool.get<double>(3 * M);
+        p.loss = pool.get<double>(3 * M); p.dinit = pool.get<double>((size_t)3 * M * nb1);
+        // the evaluation point in ONE allocation (pose | trans | latent markers | betas, each part on a 128-byte boundary): one copy per trial point
+        // instead of four (565 small copies a solve were ~3 ms of host time)
+        pose.assign((size_t)d.NPZ * NP, 0.0); trans.assign((size_t)d.NPZ * 3, 0.0); ml.assign(3 * M, 0.0); betas.assign((size_t)nb1 * (d.per_frame ? d.NPZ : 1), 0.0);
+        if (ds->betas_init && !d.per_frame) for (int e = 0; e < nb; ++e) betas[e] = ds->betas_init[e];
+        auto up16 = [](size_t c) { return (c + 15) & ~(size_t)15; };
+        pt_o_trans = up16(pose.size()); pt_o_ml = pt_o_trans + up16(trans.size()); pt_o_betas = pt_o_ml + up16(ml.size());
+        hpoint.assign(pt_o_betas + up16(betas.size()), 0.0);
+        d_point = pool.get<double>(hpoint.size());
+        p.pose = d_point; p.trans = d_point ? d_point + pt_o_trans : nullptr;
+        p.ml = d_point ? d_point + pt_o_ml : nullptr; p.betas = d_point ? d_point + pt_o_betas : nullptr;
+        p.J0 = pool.get<double>(3 * K); p.JS = pool.get<double>((size_t)std::max(1, K * nb * 3));
+        p.fp = pool.get<double>((size_t)d.NPZ * d.P); p.Rl = pool.get<double>((size_t)d.NPZ * K * 9); p.Jl = pool.get<double>((size_t)d.NPZ * K * 9);
+        p.Rw = pool.get<double>((size_t)d.NPZ * K * 9); p.tw = pool.get<double>((size_t)d.NPZ * K * 3); p.feat = pool.get<double>((size_t)d.NPZ * d.nfeat);
+        p.om = pool.get<double>((size_t)d.NPZ * K * 9); p.Bm = pool.get<double>((size_t)d.NPZ * K * 27); p.Jb = pool.get<double>((size_t)d.NPZ * K * 3);
+        p.q = pool.get<double>((size_t)d.NPZ * K * nb1 * 3); p.featzero = pool.get<int>(d.NPZ);
+        p.can = pool.get<double>((size_t)3 * d.V); p.cl = pool.get<int>(3 * M); p.cl8 = pool.get<int>(S1_NNK * M); p.coef = pool.get<double>(3 * M); p.Fc = pool.get<double>(9 * M);
+        p.dcdb = pool.get<double>((size_t)M * 3 * nb1); p.tv = pool.get<int>(3 * M); p.sdist = pool.get<double>(M);
+        p.sdp = pool.get<double>(3 * M); p.sdabc = pool.get<double>(9 * M); p.status = pool.get<int>(4);
+        p.vlist = pool.get<int>((size_t)d.NPZ * d.ncan); p.vv = pool.get<double>((size_t)d.NPZ * d.ncan * 3);
+        p.dvs = pool.get<double>((size_t)d.NPZ * d.ncan * 3 * nb1); p.dv = pool.get<double>((size_t)F * 3 * M * 3 * d.P);
+        p.vi_T = pool.get<double>((size_t)F * 3 * M * 9); p.vi_w = pool.get<double>((size_t)F * 3 * M * S1_NWMAX);
+        p.vi_x = pool.get<double>((size_t)F * 3 * M * S1_NWMAX * 3); p.vi_n = pool.get<int>((size_t)F * 3 * M); p.vi_j = pool.get<int>((size_t)F * 3 * M * S1_NWMAX);
+        p.Lb = pool.get<double>((size_t)F * M * 36 + (size_t)F * std::max(1, d.G * d.npose_prior));
+        const int n = mx.n, R = mx.R, fs = mx.fs, ns = mx.ns;
+        p.r = pool.get<double>(R); p.Jm = pool.get<double>((size_t)R * mx.ldn);
+        d_A = pool.get<double>((size_t)n * n); d_L = pool.get<double>((size_t)n * n);
+        if (want_schur) {
+            d_fcols = pool.get<int>((size_t)F * fs); d_scols = pool.get<int>(ns);
+            d_Linv = pool.get<double>((size_t)F * fs * fs); d_Y = pool.get<double>((size_t)F * fs * mx.nsp); d_z = pool.get<double>((size_t)F * fs);
+            d_T = pool.get<double>((size_t)ns * ns); d_S = pool.get<double>((size_t)ns * ns); d_h = pool.get<double>(ns); d_ds = pool.get<double>(ns);
+            d_ones = pool.get<int>((size_t)((F * fs + S1_T - 1) / S1_T) * ((ns + S1_T - 1) / S1_T));
         }
-        p.head_ids = pool.put(ds->head_ids, d.nhead, st); p.head_C = pool.put(ds->head_corr, (size_t)d.nhead_rows * d.nhead, st);
+        d_dinv = pool.get<double>((size_t)(n / S1_PB + 1) * S1_PB * S1_PB); d_flags = pool.get<int>((size_t)((R + S1_T - 1) / S1_T) * ((n + S1_T - 1) / S1_T));
+        d_g = pool.get<double>(n); d_part = pool.get<double>((size_t)S1_GT_CHUNKS * n); d_vec = pool.get<double>(n);
+        d_out = pool.get<double>(std::max(n, R));
+        if (!pool.ok) return fail(MOSHII_ERR_HIP, "stagei: device allocation failed");
+        hipMemsetAsync(p.status, 0, 4 * sizeof(int), st);
+        return 0;
     }
-    p.wt_init = pool.put(wt_init_eff.data(), M, st);
-    hipStreamSynchronize(st);
-    // the evaluation point in ONE allocation (pose | trans | latent markers | betas, each part on a 128-byte boundary): one copy per trial point
-    // instead of four (565 small copies a solve were ~3 ms of host time)
-    const size_t pt_pose = (size_t)d.NPZ * NP, pt_trans = (size_t)d.NPZ * 3, pt_ml = (size_t)3 * M, pt_betas = (size_t)std::max(1, nb) * (d.per_frame ? d.NPZ : 1);
-    auto up16 = [](size_t c) { return (c + 15) & ~(size_t)15; };
-    const size_t pt_o_trans = up16(pt_pose), pt_o_ml = pt_o_trans + up16(pt_trans), pt_o_betas = pt_o_ml + up16(pt_ml), pt_total = pt_o_betas + up16(pt_betas);
-    double* d_point = pool.get<double>(pt_total);
-    p.pose = d_point; p.trans = d_point ? d_point + pt_o_trans : nullptr;
-    p.ml = d_point ? d_point + pt_o_ml : nullptr; p.betas = d_point ? d_point + pt_o_betas : nullptr;
-    p.J0 = pool.get<double>(3 * K); p.JS = pool.get<double>((size_t)std::max(1, K * nb * 3));
-    p.fp = pool.get<double>((size_t)d.NPZ * d.P); p.Rl = pool.get<double>((size_t)d.NPZ * K * 9); p.Jl = pool.get<double>((size_t)d.NPZ * K * 9);
-    p.Rw = pool.get<double>((size_t)d.NPZ * K * 9); p.tw = pool.get<double>((size_t)d.NPZ * K * 3); p.feat = pool.get<double>((size_t)d.NPZ * d.nfeat);
-    p.om = pool.get<double>((size_t)d.NPZ * K * 9); p.Bm = pool.get<double>((size_t)d.NPZ * K * 27); p.Jb = pool.get<double>((size_t)d.NPZ * K * 3);
-    p.q = pool.get<double>((size_t)d.NPZ * K * std::max(1, nb) * 3); p.featzero = pool.get<int>(d.NPZ);
-    p.can = pool.get<double>((size_t)3 * d.V); p.cl = pool.get<int>(3 * M); p.cl8 = pool.get<int>(S1_NNK * M); p.coef = pool.get<double>(3 * M); p.Fc = pool.get<double>(9 * M);
-    p.dcdb = pool.get<double>((size_t)M * 3 * std::max(1, nb)); p.tv = pool.get<int>(3 * M); p.sdist = pool.get<double>(M);
-    p.sdp = pool.get<double>(3 * M); p.sdabc = pool.get<double>(9 * M); p.status = pool.get<int>(4);
-    p.vlist = pool.get<int>((size_t)d.NPZ * d.ncan); p.vv = pool.get<double>((size_t)d.NPZ * d.ncan * 3);
-    p.dvs = pool.get<double>((size_t)d.NPZ * d.ncan * 3 * std::max(1, nb)); p.dv = pool.get<double>((size_t)F * 3 * M * 3 * d.P);
-    p.vi_T = pool.get<double>((size_t)F * 3 * M * 9); p.vi_w = pool.get<double>((size_t)F * 3 * M * S1_NWMAX);
-    p.vi_x = pool.get<double>((size_t)F * 3 * M * S1_NWMAX * 3); p.vi_n = pool.get<int>((size_t)F * 3 * M); p.vi_j = pool.get<int>((size_t)F * 3 * M * S1_NWMAX);
-    p.Lb = pool.get<double>((size_t)F * M * 36 + (size_t)F * std::max(1, d.G * d.npose_prior));
-    // largest problem of the rounds: all of body + fingers free
-    const int npid_max = ds->n_pose_ids + ds->n_finger + nface_all;
-    const int nsh_max = d.per_frame ? F * nb : nb;
-    const int n_max = 3 * F + 3 * M + F * npid_max + nsh_max;
-    const int R_max = 3 * ntot_obs + F * (d.G ? d.npose_prior + 1 : 0) + 3 * M + nsh_max + M + F * ds->n_finger + 3 * d.nhead_rows + F * nface_all;
-    const int ld_max = (n_max + 15) & ~15;
-    p.r = pool.get<double>(R_max); p.Jm = pool.get<double>((size_t)R_max * ld_max);
-    if (n_max > S1_NMAX) return fail(MOSHII_ERR_ARG, "stagei: more than 4096 unknowns");
-    double* d_A = pool.get<double>((size_t)n_max * n_max); double* d_L = pool.get<double>((size_t)n_max * n_max);
-    // arrow-structured solver (per-frame elimination + Schur complement on the shared block) unless MOSHII_S1_SOLVER=dense asks for
-    // the dense blocked Cholesky of the whole system.  Default since round 2: ten seeded problems (six SMPL-H seeds, fingers, SMPL-X,
-    // SMPL, fixed betas) take the same dogleg iterations with both and end within 1.3e-10 (profiles/r02_stagei_schur_seeds.txt), the
-    // arrow form 1.35-1.5x faster; sharded, it sums the 169 x 169 shared block instead of the 925 x 925 system.
-    const char* solver_env = getenv("MOSHII_S1_SOLVER");
-    const bool want_schur = !(solver_env && strcmp(solver_env, "dense") == 0);
-    const int fs_max = 3 + npid_max + (d.per_frame ? nb : 0), ns_max = 3 * M + (d.per_frame ? 0 : nb), nsp_max = (ns_max + 15) & ~15;
-    int *d_fcols = nullptr, *d_scols = nullptr, *d_ones = nullptr;
-    double *d_Linv = nullptr, *d_Y = nullptr, *d_z = nullptr, *d_T = nullptr, *d_S = nullptr, *d_h = nullptr, *d_ds = nullptr;
-    if (want_schur) {
-        d_fcols = pool.get<int>((size_t)F * fs_max); d_scols = pool.get<int>(ns_max);
-        d_Linv = pool.get<double>((size_t)F * fs_max * fs_max); d_Y = pool.get<double>((size_t)F * fs_max * nsp_max); d_z = pool.get<double>((size_t)F * fs_max);
-        d_T = pool.get<double>((size_t)ns_max * ns_max); d_S = pool.get<double>((size_t)ns_max * ns_max); d_h = pool.get<double>(ns_max); d_ds = pool.get<double>(ns_max);
-        d_ones = pool.get<int>((size_t)((F * fs_max + S1_T - 1) / S1_T) * ((ns_max + S1_T - 1) / S1_T));
+
+    void upload_point() {
+        memcpy(hpoint.data(), pose.data(), pose.size() * 8);
+        memcpy(hpoint.data() + pt_o_trans, trans.data(), trans.size() * 8);
+        memcpy(hpoint.data() + pt_o_ml, ml.data(), ml.size() * 8);
+        memcpy(hpoint.data() + pt_o_betas, betas.data(), betas.size() * 8);
+        hipMemcpyAsync(d_point, hpoint.data(), hpoint.size() * 8, hipMemcpyHostToDevice, st);
     }
-    double* d_dinv = pool.get<double>((size_t)(n_max / S1_PB + 1) * S1_PB * S1_PB); int* d_flags = pool.get<int>((size_t)((R_max + S1_T - 1) / S1_T) * ((n_max + S1_T - 1) / S1_T));
-    double* d_g = pool.get<double>(n_max); double* d_part = pool.get<double>((size_t)S1_GT_CHUNKS * n_max); double* d_vec = pool.get<double>(n_max);
-    double* d_out = pool.get<double>(std::max(n_max, R_max));
-    if (!pool.ok) return fail(MOSHII_ERR_HIP, "stagei: device allocation failed");
-    hipMemsetAsync(p.status, 0, 4 * sizeof(int), st);
-
-    // ---- host state
-    std::vector<double> pose((size_t)d.NPZ * NP, 0.0), trans((size_t)d.NPZ * 3, 0.0), ml(3 * M), betas((size_t)std::max(1, nb) * (d.per_frame ? d.NPZ : 1), 0.0);
-    if (ds->betas_init && !d.per_frame) for (int e = 0; e < nb; ++e) betas[e] = ds->betas_init[e];
-    std::vector<int> pose_ids, finger_ids, colmap(NP, -1);
-
-    std::vector<double> hpoint(pt_total, 0.0);
-    auto upload_point = [&]() {
-        memcpy(hpoint.data(), pose.data(), std::min(pose.size(), pt_pose) * 8);
-        memcpy(hpoint.data() + pt_o_trans, trans.data(), std::min(trans.size(), pt_trans) * 8);
-        memcpy(hpoint.data() + pt_o_ml, ml.data(), std::min(ml.size(), pt_ml) * 8);
-        memcpy(hpoint.data() + pt_o_betas, betas.data(), std::min(betas.size(), pt_betas) * 8);
-        hipMemcpyAsync(d_point, hpoint.data(), pt_total * 8, hipMemcpyHostToDevice, st);
-    };
-    auto canonical = [&]() {   // pose kernels + canonical mesh at the uploaded point
-        LAUNCH(k_s1_pose, d.NPZ, 1, S1_TPB, st, d, p);
-        LAUNCH(k_s1_verts, (d.V + S1_TPB - 1) / S1_TPB, 1, S1_TPB, st, d, p, F, d.V, 0, p.can, 1, 1);
-    };
-    // evaluation of residual (and Jacobian) at the uploaded point
-    int shared_rows_on = 1;   // 0 during the extra rigid adjustment: the init / beta / surf / head rows are not part of its objective
-    auto evaluate = [&](int want_J) {
-        canonical();
-        LAUNCH(k_s1_knn, M, 1, S1_TPB, st, d, p, p.cl8);
-        LAUNCH(k_s1_pick3, 1, 1, S1_TPB, st, d, p, p.cl8, p.cl);
-        LAUNCH(k_s1_surface, M, 1, S1_SURF_TPB, st, d, p);
-        LAUNCH(k_s1_lists, (3 * M + S1_TPB - 1) / S1_TPB, 1, S1_TPB, st, d, p);
-        LAUNCH(k_s1_verts, (d.ncan * S1_VL + S1_TPB - 1) / S1_TPB, 1, S1_TPB, st, d, p, F, d.ncan, want_J ? 2 : 1, (double*)nullptr, 0, S1_VL);
-        if (nown > 0) LAUNCH(k_s1_verts, (3 * M * S1_VL + S1_TPB - 1) / S1_TPB, nown, S1_TPB, st, d, p, f_lo, 3 * M, want_J ? 3 : 1, (double*)nullptr, 0, S1_VL);
-        if (want_J && nown > 0) LAUNCH(k_s1_vjac, (3 * M * K + S1_TPB - 1) / S1_TPB, nown, S1_TPB, st, d, p, f_lo);
-        if (want_J) hipMemsetAsync(p.Jm, 0, (size_t)d.R * d.ldn * 8, st);
-        if (shard || !shared_rows_on) hipMemsetAsync(p.r, 0, (size_t)d.R * 8, st);          // rows of frames other ranks own (or switched off) stay zero here
-        LAUNCH(k_s1_shared, (M + S1_TPB - 1) / S1_TPB, 1, S1_TPB, st, d, p, want_J, own_shared && shared_rows_on);
-        if (d.nhead_rows && own_shared && shared_rows_on) LAUNCH(k_s1_head, 1, 1, S1_TPB, st, d, p, want_J);
-        if (nown > 0) LAUNCH(k_s1_rows, nown, want_J ? 4 : 1, S1_TPB, st, d, p, want_J, f_lo);
-    };
-    auto fetch = [&](std::vector<double>& h, const double* dev, size_t count) {
+    void fetch(Vec& h, const double* dev, size_t count) {
         h.resize(count);
         hipMemcpyAsync(h.data(), dev, count * 8, hipMemcpyDeviceToHost, st);
         hipStreamSynchronize(st);
-    };
+    }
+    void canonical(const S1Dims& e) {   // pose kernels + canonical mesh at the uploaded point
+        LAUNCH(k_s1_pose, e.NPZ, 1, S1_TPB, st, e, p);
+        LAUNCH(k_s1_verts, (e.V + S1_TPB - 1) / S1_TPB, 1, S1_TPB, st, e, p, e.F, e.V, 0, p.can, 1, 1);
+    }
+    // the facts of an evaluation and their layout become the kernels' dims
+    void set_evaluation(const sp::Facts& k_, const sp::Layout& l) {
+        k = k_; lay = l;
+        d.shape_free = k.shape_free; d.npid = k.npid; d.nfinger = k.nfinger; d.nface = k.nface;
+        d.n = l.n; d.ldn = l.ldn; d.R = l.R; d.o_ml = l.o_ml; d.o_pose = l.o_pose; d.o_b = l.o_b;
+        d.r_data = l.r_data; d.r_prior = l.r_prior; d.r_init = l.r_init; d.r_beta = l.r_beta; d.r_surf = l.r_surf; d.r_poseH = l.r_poseH;
+        d.r_head = l.r_head; d.r_poseF = l.r_poseF;
+    }
+    // residual (and Jacobian) at the uploaded point.  no_prior_: without the prior rows (the layout has none either); rows_on_ = false
+    // during the extra rigid adjustment: the init / beta / surf / head rows are not part of its objective
+    void evaluate(int want_J, bool no_prior_, bool rows_on_) {
+        S1Dims e = d;
+        if (no_prior_) e.G = 0;
+        const int M = d.M, shared_on = rows_on_ ? 1 : 0;
+        canonical(e);
+        LAUNCH(k_s1_knn, M, 1, S1_TPB, st, e, p, p.cl8);
+        LAUNCH(k_s1_pick3, 1, 1, S1_TPB, st, e, p, p.cl8, p.cl);
+        LAUNCH(k_s1_surface, M, 1, S1_SURF_TPB, st, e, p);
+        LAUNCH(k_s1_lists, (3 * M + S1_TPB - 1) / S1_TPB, 1, S1_TPB, st, e, p);
+        LAUNCH(k_s1_verts, (e.ncan * S1_VL + S1_TPB - 1) / S1_TPB, 1, S1_TPB, st, e, p, e.F, e.ncan, want_J ? 2 : 1, (double*)nullptr, 0, S1_VL);
+        if (nown > 0) LAUNCH(k_s1_verts, (3 * M * S1_VL + S1_TPB - 1) / S1_TPB, nown, S1_TPB, st, e, p, f_lo, 3 * M, want_J ? 3 : 1, (double*)nullptr, 0, S1_VL);
+        if (want_J && nown > 0) LAUNCH(k_s1_vjac, (3 * M * e.K + S1_TPB - 1) / S1_TPB, nown, S1_TPB, st, e, p, f_lo);
+        if (want_J) hipMemsetAsync(p.Jm, 0, (size_t)e.R * e.ldn * 8, st);
+        if (shard || !shared_on) hipMemsetAsync(p.r, 0, (size_t)e.R * 8, st);          // rows of frames other ranks own (or switched off) stay zero here
+        LAUNCH(k_s1_shared, (M + S1_TPB - 1) / S1_TPB, 1, S1_TPB, st, e, p, want_J, own_shared && shared_on);
+        if (e.nhead_rows && own_shared && shared_on) LAUNCH(k_s1_head, 1, 1, S1_TPB, st, e, p, want_J);
+        if (nown > 0) LAUNCH(k_s1_rows, nown, want_J ? 4 : 1, S1_TPB, st, e, p, want_J, f_lo);
+    }
 
-    // ---- setup: regressed joints, initial latent markers (vertex + normal . m2b), frozen init attachment, rigid start
-    LAUNCH(k_s1_setup, K, nb + 1, S1_TPB, st, d, p);
-    upload_point();
-    canonical();
-    std::vector<double> can;
-    fetch(can, p.can, (size_t)3 * d.V);
-    {   // prepare_mosh_markers_latent (chmosh.py:57-67); normals from the incident faces
-        for (int m = 0; m < M; ++m) {
-            int v = ds->marker_vids[m];
-            if (v < 0 || v >= d.V) return fail(MOSHII_ERR_ARG, "stagei: marker vertex id out of range");
+    // ---- start-up: regressed joints, initial latent markers (vertex + normal . m2b), frozen init attachment, rigid start
+    int startup() {
+        const int F = d.F, M = d.M, NP = d.NP;
+        LAUNCH(k_s1_setup, d.K, d.nb + 1, S1_TPB, st, d, p);
+        upload_point();
+        canonical(d);
+        Vec can;
+        fetch(can, p.can, (size_t)3 * d.V);
+        for (int m = 0; m < M; ++m) {   // prepare_mosh_markers_latent (chmosh.py:57-67); normals from the incident faces, in ascending order
+            const int v = ds->marker_vids[m];
             double nrm[3] = {0, 0, 0};
-            for (int f = 0; f < d.nfaces; ++f) {
-                const int* fv = ds->faces + 3 * f;
-                if (fv[0] != v && fv[1] != v && fv[2] != v) continue;
+            for (int i = v2f_ptr[v]; i < v2f_ptr[v + 1]; ++i) {
+                if (i > v2f_ptr[v] && v2f[i] == v2f[i - 1]) continue;          // a face that names v twice counts once
+                const int* fv = ds->faces + 3 * v2f[i];
                 double e1[3], e2[3];
                 for (int a = 0; a < 3; ++a) { e1[a] = can[3 * fv[1] + a] - can[3 * fv[0] + a]; e2[a] = can[3 * fv[2] + a] - can[3 * fv[0] + a]; }
                 nrm[0] += e1[1] * e2[2] - e1[2] * e2[1]; nrm[1] += e1[2] * e2[0] - e1[0] * e2[2]; nrm[2] += e1[0] * e2[1] - e1[1] * e2[0];
@@ -1657,299 +1731,219 @@ int moshii_stagei_core(const S1ModelView* mv, const S1PriorView* pv, const moshi
             if (ss == 0) ss = 1e-10;
             for (int a = 0; a < 3; ++a) ml[3 * m + a] = can[3 * v + a] + nrm[a] / sqrt(ss) * ds->m2b[m];
         }
-    }
-    upload_point();
-    // frozen attachment of the init markers (chmosh.py:188-190): closest0 / coef0 at the start point
-    d.shape_free = d.per_frame ? 0 : 1;
-    const int nsh0 = d.per_frame ? 0 : nb;
-    d.npid = 0; d.n = 3 * F + 3 * M + nsh0; d.ldn = (d.n + 15) & ~15; d.o_ml = 3 * F; d.o_pose = 3 * F + 3 * M; d.o_b = d.o_pose;
-    d.r_data = 0; d.r_prior = 3 * ntot_obs; d.r_init = d.r_prior; d.r_beta = d.r_init + 3 * M; d.r_surf = d.r_beta + nsh0; d.r_poseH = d.r_surf + M; d.r_head = d.r_poseH; d.r_poseF = d.r_head + 3 * d.nhead_rows; d.R = d.r_poseF;
-    d.nfinger = 0; d.nface = 0;
-    {
-        int Gkeep = d.G; d.G = 0;                      // no prior rows while the column map is empty
-        hipMemcpyAsync(d_colmap, colmap.data(), NP * sizeof(int), hipMemcpyHostToDevice, st);
-        LAUNCH(k_s1_knn, M, 1, S1_TPB, st, d, p, p.cl8);
-        LAUNCH(k_s1_pick3, 1, 1, S1_TPB, st, d, p, p.cl8, p.cl0);
-        evaluate(0);                                    // fills coef (== coef0 here) and the posed markers of every frame
-        hipMemcpyAsync(p.coef0, p.coef, 3 * M * 8, hipMemcpyDeviceToDevice, st);
-        d.G = Gkeep;
-    }
-    {   // rigid start per frame (chmosh.py:236-238, rigid_transformations.py:39-83): Procrustes on the zero-pose markers
+        upload_point();
+        {   // frozen attachment of the init markers (chmosh.py:188-190): closest0 / coef0 at the start point.  No pose columns, and no
+            // prior rows while the column map is empty
+            sp::Facts k0 = k;
+            k0.shape_free = d.per_frame ? 0 : 1; k0.npid = k0.nfinger = k0.nface = 0;
+            set_evaluation(k0, sp::layout(k0, false, true));
+            pc.colmap.assign(NP, -1);
+            hipMemcpyAsync(d_colmap, pc.colmap.data(), NP * sizeof(int), hipMemcpyHostToDevice, st);
+            LAUNCH(k_s1_knn, M, 1, S1_TPB, st, d, p, p.cl8);
+            LAUNCH(k_s1_pick3, 1, 1, S1_TPB, st, d, p, p.cl8, p.cl0);
+            evaluate(0, true, true);                        // fills coef (== coef0 here) and the posed markers of every frame
+            hipMemcpyAsync(p.coef0, p.coef, 3 * M * 8, hipMemcpyDeviceToDevice, st);
+        }
+        // rigid start per frame (chmosh.py:236-238, rigid_transformations.py:39-83): Procrustes on the zero-pose markers
         double* d_sim = pool.get<double>((size_t)3 * std::max(1, ntot_obs)); double* d_rt = pool.get<double>(6 * F);
         if (!pool.ok) return fail(MOSHII_ERR_HIP, "stagei: device allocation failed");
         hipMemsetAsync(d_rt, 0, 6 * F * 8, st);
         if (nown > 0) LAUNCH(k_s1_rigid, nown, 1, S1_TPB, st, d, p, d_sim, d_rt, f_lo);
-        std::vector<double> rt;
+        Vec rt;
         fetch(rt, d_rt, 6 * F);
-        reduce(rt.data(), 6 * F);
+        sum.reduce(rt.data(), 6 * F);
         for (int f = 0; f < F; ++f) for (int a = 0; a < 3; ++a) { pose[(size_t)f * NP + a] = rt[6 * f + a]; trans[3 * f + a] = rt[6 * f + 3 + a]; }
+        return 0;
     }
 
-    // ---- annealing rounds
-    int total_iters = 0;
-    std::vector<double> r, rnew, g, x, dsd, dgn, ddl, tmp, hbuf;
-    // round -1 (opt_settings.extra_initial_rigid_adjustment, chmosh.py:230-232): the unweighted marker residuals of all frames
-    // as a function of every frame's root orientation and translation only, e_3 = .001.  It runs through the same machinery:
-    // the only pose columns are the root's, the latent-marker and shape columns are parked behind column n (written, never
-    // read: the products take n columns of a row of ldn), the prior / init / beta / surf / head rows are off.
-    const int Gall = d.G;
-    for (int round = ds->extra_initial_rigid_adjustment ? -1 : 0; round < ds->n_anneal; ++round) {
-        const bool rigid_round = round < 0;
-        const double a = rigid_round ? 1.0 : ds->annealing[round];
-        const bool detailed = !rigid_round && round > ds->n_anneal - 3;
-        shared_rows_on = rigid_round ? 0 : 1;
-        d.G = rigid_round ? 0 : Gall;
-        pose_ids.assign(ds->pose_ids, ds->pose_ids + ds->n_pose_ids);
-        if (rigid_round) { pose_ids.clear(); pose_ids.push_back(0); pose_ids.push_back(1); pose_ids.push_back(2); }
-        finger_ids.clear();
-        if (detailed) finger_ids.assign(ds->finger_ids, ds->finger_ids + ds->n_finger);
-        pose_ids.insert(pose_ids.end(), finger_ids.begin(), finger_ids.end());
-        d.nface = (detailed && d.per_frame) ? nface_all : 0;
-        if (d.nface) pose_ids.insert(pose_ids.end(), ds->face_ids, ds->face_ids + d.nface);
-        d.shape_free = d.per_frame ? (detailed ? 1 : 0) : 1;
-        const int nsh = d.per_frame ? (d.shape_free ? F * nb : 0) : nb;
-        std::sort(pose_ids.begin(), pose_ids.end());
-        pose_ids.erase(std::unique(pose_ids.begin(), pose_ids.end()), pose_ids.end());
-        std::fill(colmap.begin(), colmap.end(), -1);
-        for (size_t c = 0; c < pose_ids.size(); ++c) colmap[pose_ids[c]] = (int)c;
-        for (int b = 0; b < d.nbody; ++b) if (ds->body_ids[b] < 0 || ds->body_ids[b] >= NP) return fail(MOSHII_ERR_ARG, "stagei: body id out of range");
-        d.npid = (int)pose_ids.size(); d.nfinger = (int)finger_ids.size();
-        d.n = 3 * F + 3 * M + F * d.npid + nsh; d.ldn = (d.n + 15) & ~15;
-        d.o_ml = 3 * F; d.o_pose = 3 * F + 3 * M; d.o_b = d.o_pose + F * d.npid;
-        if (rigid_round) { d.n = 6 * F; d.ldn = ld_max; d.o_pose = 3 * F; d.o_ml = 6 * F; d.o_b = 6 * F + 3 * M; }
-        d.r_data = 0; d.r_prior = 3 * ntot_obs; d.r_init = d.r_prior + F * (d.G ? d.npose_prior + 1 : 0);
-        d.r_beta = d.r_init + 3 * M; d.r_surf = d.r_beta + nsh; d.r_poseH = d.r_surf + M; d.r_head = d.r_poseH + F * d.nfinger;
-        d.r_poseF = d.r_head + 3 * d.nhead_rows; d.R = d.r_poseF + F * d.nface;
-        p.w_anneal = a; p.w_data = rigid_round ? 1.0 : (ds->wt_data / a) * (46.0 / M); p.w_poseB = ds->wt_poseB * a; p.w_poseH = ds->wt_poseH * a;
+    // ---- one annealing round.  Round -1 (opt_settings.extra_initial_rigid_adjustment, chmosh.py:230-232): the unweighted marker
+    // residuals of all frames as a function of every frame's root orientation and translation only, e_3 = .001.  It runs through the
+    // same machinery: the only pose columns are the root's, the latent-marker and shape columns are parked behind column n, the
+    // prior / init / beta / surf / head rows are off.
+    void begin_round(int round) {
+        const int F = d.F, M = d.M;
+        rigid = round < 0;
+        const double a = rigid ? 1.0 : ds->annealing[round];
+        const bool detailed = !rigid && round > ds->n_anneal - 3;
+        no_prior = rigid; rows_on = !rigid;
+        pc = sp::pose_columns(d.NP, ds->pose_ids, ds->n_pose_ids, ds->finger_ids, ds->n_finger, ds->face_ids, nface_all, rigid, detailed);
+        sp::Facts kr = k;
+        kr.shape_free = d.per_frame ? (detailed ? 1 : 0) : 1;
+        kr.npid = (int)pc.pose_ids.size(); kr.nfinger = (int)pc.finger_ids.size(); kr.nface = pc.nface;
+        set_evaluation(kr, sp::layout(kr, rigid, no_prior, mx.ldn));
+        p.w_anneal = a; p.w_data = rigid ? 1.0 : (ds->wt_data / a) * (46.0 / M); p.w_poseB = ds->wt_poseB * a; p.w_poseH = ds->wt_poseH * a;
         p.w_beta = (d.per_frame ? ds->wt_expr : ds->wt_betas) * a; p.w_surf = ds->wt_surf; p.w_init_head = ds->wt_init_head * a;
         p.w_poseF = ds->wt_poseF * a;
-        hipMemcpyAsync(d_colmap, colmap.data(), NP * sizeof(int), hipMemcpyHostToDevice, st);
-        if (d.nfinger) hipMemcpyAsync(d_finger, finger_ids.data(), d.nfinger * sizeof(int), hipMemcpyHostToDevice, st);
-        const int fs = 3 + d.npid + ((d.per_frame && d.shape_free) ? nb : 0), ns = 3 * M + (d.per_frame ? 0 : nb), nsp = (ns + 15) & ~15;
-        const bool schur = want_schur && fs <= S1_FSMAX && !rigid_round;
+        hipMemcpyAsync(d_colmap, pc.colmap.data(), d.NP * sizeof(int), hipMemcpyHostToDevice, st);
+        if (d.nfinger) hipMemcpyAsync(d_finger, pc.finger_ids.data(), d.nfinger * sizeof(int), hipMemcpyHostToDevice, st);
+        schur = want_schur && lay.fs <= S1_FSMAX && !rigid;
+        std::vector<int> fcols, scols, ones;
         if (schur) {
-            std::vector<int> fcols((size_t)F * fs), scols(ns), ones((size_t)((F * fs + S1_T - 1) / S1_T) * ((ns + S1_T - 1) / S1_T), 1);
-            for (int f = 0; f < F; ++f) {
-                int* fc = fcols.data() + (size_t)f * fs;
-                for (int c = 0; c < 3; ++c) fc[c] = 3 * f + c;
-                for (int c = 0; c < d.npid; ++c) fc[3 + c] = d.o_pose + f * d.npid + c;
-                for (int e = 0; e < fs - 3 - d.npid; ++e) fc[3 + d.npid + e] = d.o_b + f * nb + e;
-            }
-            for (int i = 0; i < 3 * M; ++i) scols[i] = d.o_ml + i;
-            for (int e = 0; e < ns - 3 * M; ++e) scols[3 * M + e] = d.o_b + e;
+            sp::arrow_tables(k, lay, fcols, scols);
+            ones.assign((size_t)((F * lay.fs + S1_T - 1) / S1_T) * ((lay.ns + S1_T - 1) / S1_T), 1);
             hipMemcpyAsync(d_fcols, fcols.data(), fcols.size() * sizeof(int), hipMemcpyHostToDevice, st);
             hipMemcpyAsync(d_scols, scols.data(), scols.size() * sizeof(int), hipMemcpyHostToDevice, st);
             hipMemcpyAsync(d_ones, ones.data(), ones.size() * sizeof(int), hipMemcpyHostToDevice, st);
         }
         hipStreamSynchronize(st);
-        const int n = d.n, R = d.R;
-        auto pack = [&](std::vector<double>& xx) {
-            xx.resize(n);
-            for (int f = 0; f < F; ++f) for (int c = 0; c < 3; ++c) xx[3 * f + c] = trans[3 * f + c];
-            if (!rigid_round) for (int i = 0; i < 3 * M; ++i) xx[d.o_ml + i] = ml[i];
-            for (int f = 0; f < F; ++f) for (int c = 0; c < d.npid; ++c) xx[d.o_pose + f * d.npid + c] = pose[(size_t)f * NP + pose_ids[c]];
-            if (!rigid_round) for (int e = 0; e < nsh; ++e) xx[d.o_b + e] = betas[e];          // per-frame mode: [frame][coefficient], canonical row last
-        };
-        auto unpack = [&](const std::vector<double>& xx) {
-            for (int f = 0; f < F; ++f) for (int c = 0; c < 3; ++c) trans[3 * f + c] = xx[3 * f + c];
-            if (!rigid_round) for (int i = 0; i < 3 * M; ++i) ml[i] = xx[d.o_ml + i];
-            for (int f = 0; f < F; ++f) for (int c = 0; c < d.npid; ++c) pose[(size_t)f * NP + pose_ids[c]] = xx[d.o_pose + f * d.npid + c];
-            if (!rigid_round) for (int e = 0; e < nsh; ++e) betas[e] = xx[d.o_b + e];
-        };
-        auto eval_at = [&](const std::vector<double>& xx, int want_J, std::vector<double>& rr) -> double {
-            unpack(xx); upload_point(); evaluate(want_J); fetch(rr, p.r, R);
-            double sse_ = dotv(rr, rr);
-            reduce(&sse_, 1);
-            return sse_;
-        };
-        auto normal_eq = [&]() {     // A = J^T J, g = -J^T r on the device; g to the host
-            int nt = (n + S1_T - 1) / S1_T;
-            LAUNCH(k_s1_nzflags, (R + S1_T - 1) / S1_T, nt, 256, st, p.Jm, R, n, d.ldn, d_flags);
-            LAUNCH(k_s1_syrk, nt, nt, 256, st, p.Jm, R, n, d.ldn, d_A, d_flags);
-            LAUNCH(k_s1_gemv_t, (n + S1_TPB - 1) / S1_TPB, S1_GT_CHUNKS, S1_TPB, st, p.Jm, p.r, R, n, d.ldn, d_part);
-            LAUNCH(k_s1_gemv_t_sum, (n + S1_TPB - 1) / S1_TPB, 1, S1_TPB, st, d_part, n, -1.0, d_g);
-            if (shard && schur) {   // arrow-structured solver: A stays rank-local; only the gradient (and later the Schur block) is summed
-                fetch(g, d_g, n);
-                reduce(g.data(), n);
-                return;
-            }
-            if (shard) {        // sum the ranks' normal equations A and g (MOSHII_S1_SOLVER=dense: a few MB per iteration)
-                reduce_dev(d_A, (long long)n * n);
-                reduce_dev(d_g, n);
-            }
+    }
+    void pack(Vec& x) const {
+        const int F = d.F, NP = d.NP, npid = d.npid;
+        x.resize(lay.n);
+        for (int f = 0; f < F; ++f) for (int c = 0; c < 3; ++c) x[3 * f + c] = trans[3 * f + c];
+        if (!rigid) for (int i = 0; i < 3 * d.M; ++i) x[lay.o_ml + i] = ml[i];
+        for (int f = 0; f < F; ++f) for (int c = 0; c < npid; ++c) x[lay.o_pose + f * npid + c] = pose[(size_t)f * NP + pc.pose_ids[c]];
+        if (!rigid) for (int e = 0; e < lay.nsh; ++e) x[lay.o_b + e] = betas[e];          // per-frame mode: [frame][coefficient], canonical row last
+    }
+    void unpack(const Vec& x) {
+        const int F = d.F, NP = d.NP, npid = d.npid;
+        for (int f = 0; f < F; ++f) for (int c = 0; c < 3; ++c) trans[3 * f + c] = x[3 * f + c];
+        if (!rigid) for (int i = 0; i < 3 * d.M; ++i) ml[i] = x[lay.o_ml + i];
+        for (int f = 0; f < F; ++f) for (int c = 0; c < npid; ++c) pose[(size_t)f * NP + pc.pose_ids[c]] = x[lay.o_pose + f * npid + c];
+        if (!rigid) for (int e = 0; e < lay.nsh; ++e) betas[e] = x[lay.o_b + e];
+    }
+    // the dogleg's problem (stagei_plan.h)
+    double eval(const Vec& x, bool want_J) {
+        unpack(x); upload_point(); evaluate(want_J ? 1 : 0, no_prior, rows_on); fetch(r, p.r, lay.R);
+        double sse = sp::dotv(r, r);
+        sum.reduce(&sse, 1);
+        return sse;
+    }
+    void normal_eq(Vec& g) {     // A = J^T J, g = -J^T r on the device; g to the host
+        const int n = lay.n, R = lay.R, nt = (n + S1_T - 1) / S1_T;
+        LAUNCH(k_s1_nzflags, (R + S1_T - 1) / S1_T, nt, 256, st, p.Jm, R, n, d.ldn, d_flags);
+        LAUNCH(k_s1_syrk, nt, nt, 256, st, p.Jm, R, n, d.ldn, d_A, d_flags);
+        LAUNCH(k_s1_gemv_t, (n + S1_TPB - 1) / S1_TPB, S1_GT_CHUNKS, S1_TPB, st, p.Jm, p.r, R, n, d.ldn, d_part);
+        LAUNCH(k_s1_gemv_t_sum, (n + S1_TPB - 1) / S1_TPB, 1, S1_TPB, st, d_part, n, -1.0, d_g);
+        if (shard && schur) {   // arrow-structured solver: A stays rank-local; only the gradient (and later the Schur block) is summed
             fetch(g, d_g, n);
-        };
-        auto Ax = [&](const std::vector<double>& v, std::vector<double>& out) {   // A . v (A must still be unfactored)
-            hipMemcpyAsync(d_vec, v.data(), n * 8, hipMemcpyHostToDevice, st);
-            LAUNCH(k_s1_gemv, n, 1, S1_TPB, st, d_A, d_vec, n, n, d_out);
-            fetch(out, d_out, n);
-            if (shard && schur) reduce(out.data(), n);          // A is rank-local there: sum the products
-        };
-        // ---- Powell dogleg (chumpy minimize_dogleg as restated in oracle/stageii_oracle.py:minimize_dogleg)
-        const double e1 = 1e-15, e2 = 1e-15, e3 = rigid_round ? .001 : ds->stagei_lr;
+            sum.reduce(g.data(), n);
+            return;
+        }
+        if (shard) {        // sum the ranks' normal equations A and g (MOSHII_S1_SOLVER=dense: a few MB per iteration)
+            sum.reduce_dev(d_A, (long long)n * n);
+            sum.reduce_dev(d_g, n);
+        }
+        fetch(g, d_g, n);
+    }
+    void Ax(const Vec& v, Vec& out) {   // A . v (A must still be unfactored)
+        const int n = lay.n;
+        hipMemcpyAsync(d_vec, v.data(), n * 8, hipMemcpyHostToDevice, st);
+        LAUNCH(k_s1_gemv, n, 1, S1_TPB, st, d_A, d_vec, n, n, d_out);
+        fetch(out, d_out, n);
+        if (shard && schur) sum.reduce(out.data(), n);          // A is rank-local there: sum the products
+    }
+    void gn_step(Vec& dgn) {
+        const int n = lay.n;
+        if (schur) {
+            const S1Arrow a{d_A, n, d_g, d_fcols, d.F, lay.fs, d_scols, lay.ns, lay.nsp, d_ones, d_Linv, d_Y, d_z, d_T, d_S, d_h, d_dinv, d_ds, p.status, f_lo, nown};
+            s1_arrow_reduce(a, st);
+            if (shard) {   // the only matrix that crosses ranks: the Schur system of the shared block, in place on the device
+                sum.reduce_dev(d_S, (long long)lay.ns * lay.ns);
+                sum.reduce_dev(d_h, lay.ns);
+            }
+            s1_arrow_solve(a, d_out, true, own_shared, st);
+            fetch(dgn, d_out, n);
+            if (shard) sum.reduce(dgn.data(), n);
+            return;
+        }
+        // the factorisation overwrites A: keep a copy for the rho denominator products
+        hipMemcpyAsync(d_L, d_A, (size_t)n * n * 8, hipMemcpyDeviceToDevice, st);
+        s1_chol_factor(d_L, n, d_dinv, p.status, st);
+        LAUNCH(k_s1_tri_solve, 1, 1, S1_CHOL_TPB, st, d_L, n, d_dinv, d_g, d_out);
+        fetch(dgn, d_out, n);
+    }
+    // after the last round: stagei_markers_sim_all, the error terms and the markers' init offsets
+    int report_errors() {
+        const int F = d.F, M = d.M;
+        upload_point(); evaluate(0, no_prior, rows_on); fetch(r, p.r, lay.R);
+        if (ds->markers_sim) {       // stagei_markers_sim_all (chmosh.py:441): every latent marker on every frame's body
+            double* d_simall = pool.get<double>((size_t)F * M * 3);
+            if (!pool.ok) return fail(MOSHII_ERR_HIP, "stagei: device allocation failed");
+            hipMemsetAsync(d_simall, 0, (size_t)F * M * 3 * 8, st);
+            if (nown > 0) LAUNCH(k_s1_simall, nown, 1, S1_TPB, st, d, p, d_simall, f_lo);
+            Vec sa;
+            fetch(sa, d_simall, (size_t)F * M * 3);
+            sum.reduce(sa.data(), (long long)F * M * 3);
+            memcpy(ds->markers_sim, sa.data(), sa.size() * 8);
+        }
+        auto sse_rows = [&](int lo, int hi) { double s = 0; for (int i = lo; i < hi; ++i) s += r[i] * r[i]; return s; };
+        // (the collectives below are issued whether or not THIS rank asked for the output: ranks whose callers differ in which
+        //  optional pointers they set must still issue the same sequence of all-reduces)
+        const int row[9] = {lay.r_data, lay.r_prior, lay.r_init, lay.r_beta, lay.r_surf, lay.r_poseH, lay.r_head, lay.r_poseF, lay.R};
+        Vec ev(8 + (size_t)M);
+        for (int t = 0; t < 8; ++t) ev[t] = sse_rows(row[t], row[t + 1]);
+        // rows r_init + 3 m .. + 3: marker m's weighted offset from its initial placement; summed over ranks like errs[2]
+        for (int mk = 0; mk < M; ++mk) ev[8 + mk] = sse_rows(lay.r_init + 3 * mk, lay.r_init + 3 * mk + 3);
+        sum.reduce(ev.data(), 8);
+        sum.reduce(ev.data() + 8, M);
+        if (ds->errs) memcpy(ds->errs, ev.data(), 8 * sizeof(double));
+        if (ds->init_sq) memcpy(ds->init_sq, ev.data() + 8, (size_t)M * sizeof(double));
+        return 0;
+    }
+    int solve_round(int round) {
+        begin_round(round);
+        sp::DoglegControl ctl;                  // e_1 = e_2 = 1e-15, delta_0 = 0.5
+        ctl.e3 = rigid ? .001 : ds->stagei_lr; ctl.maxiter = ds->maxiter;
+        Vec x;
         pack(x);
-        double sse = eval_at(x, 1, r);
-        normal_eq();
-        double delta = 0.5;
-        bool done = false;
-        int iteration = 0;
-        auto norminf = [](const std::vector<double>& v) { double s = 0; for (double t : v) s = std::max(s, fabs(t)); return s; };
-        if (norminf(g) < e1) done = true;
-        std::vector<double> Ag, xt;
-        while (!done) {
-            ++iteration;
-            // |J g|^2 = g^T A g
-            Ax(g, Ag);
-            double gg = dotv(g, g), gAg = dotv(g, Ag);
-            dsd = g;
-            for (double& t : dsd) t *= gg / gAg;
-            bool have_gn = false;
-            while (true) {
-                double nsd = nrm2(dsd);
-                if (nsd >= delta) { ddl = dsd; for (double& t : ddl) t *= delta / nsd; }
-                else {
-                    if (!have_gn && schur) {
-                        const size_t lds_bytes = ((size_t)fs * (fs + 1) + 2 * (size_t)fs) * sizeof(double);
-                        hipMemsetAsync(d_Y, 0, (size_t)F * fs * nsp * 8, st);
-                        hipMemsetAsync(d_z, 0, (size_t)F * fs * 8, st);
-                        hipFuncSetAttribute(reinterpret_cast<const void*>(k_s1_elim), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-                        // (sharded: every rank eliminates its own frames -- their rows live only here, so A_ff, A_fs and g_f are complete --
-                        //  and contributes A_ss,r - Y_r^T Y_r and g_s,r - Y_r^T z_r; the sum over ranks is the Schur system: ns^2 + ns doubles)
-                        if (nown > 0) LAUNCH_LDS(k_s1_elim, nown, 1, S1_TPB, lds_bytes, st, d_A, n, d_g, d_fcols, fs, d_scols, ns, nsp, d_Linv, d_Y, d_z, p.status, f_lo);
-                        if (nown > 0) {
-                            const size_t ybytes = ((size_t)fs * (fs + 1) + (size_t)S1_YC * fs) * sizeof(double);
-                            hipFuncSetAttribute(reinterpret_cast<const void*>(k_s1_elim_y), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ybytes);
-                            LAUNCH_LDS(k_s1_elim_y, nown, (ns + 1 + S1_YC - 1) / S1_YC, S1_TPB, ybytes, st, d_A, n, d_g, d_fcols, fs, d_scols, ns, nsp, d_Linv, d_Y, d_z, f_lo);
-                        }
-                        { int nt = (ns + S1_T - 1) / S1_T; LAUNCH(k_s1_syrk, nt, nt, 256, st, d_Y, F * fs, ns, nsp, d_T, d_ones); }
-                        LAUNCH(k_s1_schur_sub, ns, 1, S1_TPB, st, d_A, n, d_g, d_scols, ns, d_T, d_Y, nsp, d_z, F * fs, d_S, d_h);
-                        if (shard) {   // the only matrix that crosses ranks: the Schur system of the shared block, in place on the device
-                            reduce_dev(d_S, (long long)ns * ns);
-                            reduce_dev(d_h, ns);
-                        }
-                        for (int j0 = 0; j0 < ns; j0 += S1_PB) {
-                            const int jb = std::min(S1_PB, ns - j0), rem = ns - j0 - jb;
-                            LAUNCH(k_s1_chol_diag, 1, 1, S1_TRSM_TPB, st, d_S, ns, j0, d_dinv, p.status);
-                            if (rem > 0) LAUNCH(k_s1_chol_trsm, (rem + S1_TRSM_TPB - 1) / S1_TRSM_TPB, 1, S1_TRSM_TPB, st, d_S, ns, j0, d_dinv);
-                            if (rem > 0) { int nt = (rem + S1_PB - 1) / S1_PB; LAUNCH(k_s1_chol_update, nt, nt, 256, st, d_S, ns, j0, jb); }
-                        }
-                        LAUNCH(k_s1_tri_solve, 1, 1, S1_CHOL_TPB, st, d_S, ns, d_dinv, d_h, d_ds);
-                        hipMemsetAsync(d_out, 0, (size_t)n * 8, st);
-                        if (nown > 0) LAUNCH(k_s1_back, nown, 1, S1_TPB, st, d_fcols, fs, d_scols, ns, nsp, d_Linv, d_Y, d_z, d_ds, d_out, f_lo, own_shared);
-                        else if (own_shared) return fail(MOSHII_ERR_ARG, "stagei: the rank that owns the shared rows must own at least one frame");
-                        fetch(dgn, d_out, n);
-                        if (shard) reduce(dgn.data(), n);
-                        have_gn = true;
-                    }
-                    if (!have_gn) {
-                        // the factorisation overwrites A: keep a copy for the rho denominator products
-                        hipMemcpyAsync(d_L, d_A, (size_t)n * n * 8, hipMemcpyDeviceToDevice, st);
-                        for (int j0 = 0; j0 < n; j0 += S1_PB) {
-                            const int jb = std::min(S1_PB, n - j0), rem = n - j0 - jb;
-                            LAUNCH(k_s1_chol_diag, 1, 1, S1_TRSM_TPB, st, d_L, n, j0, d_dinv, p.status);
-                            if (rem > 0) LAUNCH(k_s1_chol_trsm, (rem + S1_TRSM_TPB - 1) / S1_TRSM_TPB, 1, S1_TRSM_TPB, st, d_L, n, j0, d_dinv);
-                            if (rem > 0) { int nt = (rem + S1_PB - 1) / S1_PB; LAUNCH(k_s1_chol_update, nt, nt, 256, st, d_L, n, j0, jb); }
-                        }
-                        LAUNCH(k_s1_tri_solve, 1, 1, S1_CHOL_TPB, st, d_L, n, d_dinv, d_g, d_out);
-                        fetch(dgn, d_out, n);
-                        have_gn = true;
-                    }
-                    double ngn = nrm2(dgn);
-                    if (ngn <= delta) ddl = dgn;
-                    else {
-                        double dsq = delta * delta, sq_sd = nsd * nsd, dd = 0, dsdd = 0;
-                        for (int i = 0; i < n; ++i) { double df = dgn[i] - dsd[i]; dd += df * df; dsdd += df * dsd[i]; }
-                        double gs = dotv(dgn, dsd);
-                        double pnow = dd * dsq + gs * gs - ngn * ngn * sq_sd;
-                        double beta = (dsq - sq_sd) / (dsdd + sqrt(pnow));
-                        ddl.resize(n);
-                        for (int i = 0; i < n; ++i) ddl[i] = dsd[i] + beta * (dgn[i] - dsd[i]);
-                    }
-                }
-                double step = nrm2(ddl);
-                bool improved = false;
-                if (step <= e2 * nrm2(x)) done = true;
-                else {
-                    xt = x;
-                    for (int i = 0; i < n; ++i) xt[i] += ddl[i];
-                    const double sse_new = eval_at(xt, 0, rnew);
-                    double rho = sse - sse_new;
-                    if (rho > 0) {
-                        Ax(ddl, tmp);
-                        rho = rho / (2.0 * dotv(g, ddl) - dotv(ddl, tmp));
-                    }
-                    improved = rho > 0;
-                    if (improved) {
-                        x = xt;
-                        if (e3 > 0 && (sse - sse_new) / sse < e3) done = true;
-                        else {
-                            sse = eval_at(x, 1, r);
-                            normal_eq();
-                            if (norminf(g) < e1) done = true;
-                        }
-                    }
-                    if (rho > 0.9) delta = std::max(delta, 2.5 * step);
-                    else if (rho < 0.05) delta *= 0.25;
-                    if (delta <= e2 * nrm2(x)) done = true;
-                }
-                if (done || improved) break;
-            }
-            if (iteration >= ds->maxiter) done = true;
-        }
-        total_iters += iteration;
+        total_iters += sp::dogleg(*this, x, ctl);
         unpack(x);
-        if (round == ds->n_anneal - 1) {
-            upload_point(); evaluate(0); fetch(r, p.r, R);
-            if (ds->markers_sim) {       // stagei_markers_sim_all (chmosh.py:441): every latent marker on every frame's body
-                double* d_simall = pool.get<double>((size_t)F * M * 3);
-                if (!pool.ok) return fail(MOSHII_ERR_HIP, "stagei: device allocation failed");
-                hipMemsetAsync(d_simall, 0, (size_t)F * M * 3 * 8, st);
-                if (nown > 0) LAUNCH(k_s1_simall, nown, 1, S1_TPB, st, d, p, d_simall, f_lo);
-                std::vector<double> sa;
-                fetch(sa, d_simall, (size_t)F * M * 3);
-                reduce(sa.data(), (long long)F * M * 3);
-                memcpy(ds->markers_sim, sa.data(), sa.size() * 8);
-            }
-            auto sse_rows = [&](int lo, int hi) { double s = 0; for (int i = lo; i < hi; ++i) s += r[i] * r[i]; return s; };
-            {   // (the collectives below are issued whether or not THIS rank asked for the output: ranks whose callers differ in which
-                //  optional pointers they set must still issue the same sequence of all-reduces)
-                std::vector<double> ev(8 + (size_t)M);
-                ev[0] = sse_rows(d.r_data, d.r_prior); ev[1] = sse_rows(d.r_prior, d.r_init); ev[2] = sse_rows(d.r_init, d.r_beta);
-                ev[3] = sse_rows(d.r_beta, d.r_surf); ev[4] = sse_rows(d.r_surf, d.r_poseH); ev[5] = sse_rows(d.r_poseH, d.r_head); ev[6] = sse_rows(d.r_head, d.r_poseF); ev[7] = sse_rows(d.r_poseF, d.R);
-                // rows r_init + 3 m .. + 3: marker m's weighted offset from its initial placement; summed over ranks like errs[2]
-                for (int mk = 0; mk < M; ++mk) ev[8 + mk] = sse_rows(d.r_init + 3 * mk, d.r_init + 3 * mk + 3);
-                reduce(ev.data(), 8);
-                reduce(ev.data() + 8, M);
-                if (ds->errs) memcpy(ds->errs, ev.data(), 8 * sizeof(double));
-                if (ds->init_sq) memcpy(ds->init_sq, ev.data() + 8, (size_t)M * sizeof(double));
-            }
-        }
+        if (round == ds->n_anneal - 1) if (int rc = report_errors()) return rc;
         int hstat[4];
         hipMemcpyAsync(hstat, p.status, sizeof(hstat), hipMemcpyDeviceToHost, st);
         hipStreamSynchronize(st);
-        if (reduce_rc) return fail(MOSHII_ERR_ARG, "stagei: the all-reduce callback failed");
+        if (sum.rc) return fail(MOSHII_ERR_ARG, "stagei: the all-reduce callback failed");
         if (hstat[0] == 3) return fail(MOSHII_ERR_ARG, "stagei: a vertex has more than 16 non-zero skinning weights");
         if (hstat[1]) return fail(MOSHII_ERR_NUMERIC, "stagei: normal equations not positive definite");
         if (hstat[2]) return fail(MOSHII_ERR_NUMERIC, "stagei: a marker's nearest vertices are collinear for every one of its 8 neighbours (transformed_lm.py:94-101 runs out of candidates)");
+        return 0;
     }
-    if (hipGetLastError() != hipSuccess) return fail(MOSHII_ERR_HIP, "stagei: kernel launch failed");
+
     // ---- outputs; nearest canonical vertex of every latent marker (chmosh.py:420-422)
-    upload_point(); canonical();
-    fetch(can, p.can, (size_t)3 * d.V);
-    for (int m = 0; m < M; ++m) {
-        double best = 1e300; int bi = 0;
-        for (int v = 0; v < d.V; ++v) {
-            double s = 0;
-            for (int a = 0; a < 3; ++a) { double t = ml[3 * m + a] - can[3 * v + a]; s += t * t; }
-            if (s < best) { best = s; bi = v; }
+    void outputs() {
+        const int F = d.F, M = d.M, nb = d.nb;
+        upload_point(); canonical(d);
+        Vec can;
+        fetch(can, p.can, (size_t)3 * d.V);
+        for (int m = 0; m < M; ++m) {
+            double best = 1e300; int bi = 0;
+            for (int v = 0; v < d.V; ++v) {
+                double s = 0;
+                for (int a = 0; a < 3; ++a) { double t = ml[3 * m + a] - can[3 * v + a]; s += t * t; }
+                if (s < best) { best = s; bi = v; }
+            }
+            if (ds->markers_latent_vids) ds->markers_latent_vids[m] = bi;
         }
-        if (ds->markers_latent_vids) ds->markers_latent_vids[m] = bi;
+        if (ds->betas && !d.per_frame) for (int e = 0; e < nb; ++e) ds->betas[e] = betas[e];
+        if (ds->expression && d.per_frame) memcpy(ds->expression, betas.data(), (size_t)F * nb * 8);
+        if (ds->markers_latent) memcpy(ds->markers_latent, ml.data(), 3 * M * 8);
+        if (ds->pose) memcpy(ds->pose, pose.data(), (size_t)F * d.NP * 8);
+        if (ds->trans) memcpy(ds->trans, trans.data(), (size_t)F * 3 * 8);
+        if (ds->iters) ds->iters[0] = total_iters;
     }
-    if (ds->betas && !d.per_frame) for (int e = 0; e < nb; ++e) ds->betas[e] = betas[e];
-    if (ds->expression && d.per_frame) memcpy(ds->expression, betas.data(), (size_t)F * nb * 8);
-    if (ds->markers_latent) memcpy(ds->markers_latent, ml.data(), 3 * M * 8);
-    if (ds->pose) memcpy(ds->pose, pose.data(), (size_t)F * NP * 8);
-    if (ds->trans) memcpy(ds->trans, trans.data(), (size_t)F * 3 * 8);
-    if (ds->iters) ds->iters[0] = total_iters;
-    return MOSHII_OK;
+
+    int run() {
+        if (int rc = check()) return rc;
+        const char* msg = "";
+        // the staging buffer of the rank sums: >= n, 3 F M, 6 F
+        const long long cap0 = 3LL * d.M + (long long)d.F * (3 + d.NP) + (long long)d.nb * (d.per_frame ? d.F : 1) + 3LL * d.F * d.M + 6LL * d.F + 64;
+        if (int rc = sum.verdict(bad_range, bad_owner, cap0, &msg)) return fail(rc, msg);
+        upload_constants();
+        if (int rc = allocate()) return rc;
+        if (int rc = startup()) return rc;
+        for (int round = ds->extra_initial_rigid_adjustment ? -1 : 0; round < ds->n_anneal; ++round)
+            if (int rc = solve_round(round)) return rc;
+        if (hipGetLastError() != hipSuccess) return fail(MOSHII_ERR_HIP, "stagei: kernel launch failed");
+        outputs();
+        return MOSHII_OK;
+    }
+};
+
+}  // namespace
+
+// One Stage-I solve.  `mv` / `pv`: device views of the model / prior (moshii_api.hip fills them from the handles).
+int moshii_stagei_core(const S1ModelView* mv, const S1PriorView* pv, const moshii_stagei_desc* ds, void* stream_, char* err, int errlen) {
+    S1Solve s(mv, pv, ds, (hipStream_t)stream_, err, errlen);
+    return s.run();
 }

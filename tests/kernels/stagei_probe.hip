@@ -5,7 +5,9 @@
 //
 // Every launcher takes host arrays.  An output argument is the WHOLE host buffer, guard bands included: it is uploaded as it is (so the
 // device copy carries the caller's sentinels), the kernels get the pointer `PG` elements in, and all of it is copied back -- what the
-// kernels wrote outside their range shows up in the guards.  status words are copied both ways without guards.  Launches follow moshii_stagei_core: same grids, threads and dynamic LDS.
+// kernels wrote outside their range shows up in the guards.  status words are copied both ways without guards.  The factorisation and
+// the arrow step are the product's own launch sequences (s1_chol_factor, s1_arrow_reduce, s1_arrow_solve); the single launches follow
+// moshii_stagei_core: same grids, threads and dynamic LDS.
 // Return: 0, or -1 if a HIP call failed.
 #include "../../moshpp_amd/csrc/stagei.hip"
 
@@ -42,15 +44,6 @@ struct Probe {
     }
 };
 
-// the panel loop of the blocked Cholesky as the host runs it (moshii_stagei_core: the Schur block and the dense path)
-void chol_panels(double* A, int n, double* dinv, int* status) {
-    for (int j0 = 0; j0 < n; j0 += S1_PB) {
-        const int jb = std::min(S1_PB, n - j0), rem = n - j0 - jb;
-        LAUNCH(k_s1_chol_diag, 1, 1, S1_TRSM_TPB, 0, A, n, j0, dinv, status);
-        if (rem > 0) LAUNCH(k_s1_chol_trsm, (rem + S1_TRSM_TPB - 1) / S1_TRSM_TPB, 1, S1_TRSM_TPB, 0, A, n, j0, dinv);
-        if (rem > 0) { int nt = (rem + S1_PB - 1) / S1_PB; LAUNCH(k_s1_chol_update, nt, nt, 256, 0, A, n, j0, jb); }
-    }
-}
 }  // namespace
 
 extern "C" {
@@ -103,14 +96,14 @@ int probe_chol(double* A, int n, double* dinv, const double* g, double* x, int* 
     double* dx = pr.out(x, (size_t)n);
     int* dS = pr.io(status, 3);
     if (!pr.ok) return pr.finish();
-    chol_panels(dA, n, dD, dS);
+    s1_chol_factor(dA, n, dD, dS, 0);
     LAUNCH(k_s1_tri_solve, 1, 1, S1_CHOL_TPB, 0, dA, n, dD, dg, dx);
     return pr.finish();
 }
 
-// The arrow-structured Gauss-Newton step of moshii_stagei_core on the frames [fbase, fbase + nown) of F: k_s1_elim, k_s1_elim_y, the
-// SYRK of Y (all-ones flags), k_s1_schur_sub, the blocked Cholesky of S, k_s1_tri_solve, k_s1_back.  A: n x n (lower part read), g: n,
-// fcols: F x fs, scols: ns.  Outputs (guarded): Linv F x fs x fs, Y F x fs x nsp, z F x fs, T / S ns x ns, h / ds ns, dinv, out n (NOT
+// The arrow-structured Gauss-Newton step of moshii_stagei_core on the frames [fbase, fbase + nown) of F, both halves as the solver runs
+// them (no rank sum in between): k_s1_elim, k_s1_elim_y, the SYRK of Y (all-ones flags), k_s1_schur_sub; the blocked Cholesky of S,
+// k_s1_tri_solve, k_s1_back.  A: n x n (lower part read), g: n, fcols: F x fs, scols: ns.  Outputs (guarded): Linv F x fs x fs, Y F x fs x nsp, z F x fs, T / S ns x ns, h / ds ns, dinv, out n (NOT
 // cleared first: the caller's fill shows which entries k_s1_back wrote).
 int probe_schur(const double* A, int n, const double* g, const int* fcols, int F, int fs, const int* scols, int ns, int fbase, int nown,
                 int scatter_shared, double* Linv, double* Y, double* z, double* T, double* S, double* h, double* dinv, double* ds,
@@ -128,19 +121,9 @@ int probe_schur(const double* A, int n, const double* g, const int* fcols, int F
     double* dout = pr.out(out, (size_t)n);
     int* dst = pr.io(status, 3);
     if (!pr.ok) return pr.finish();
-    const size_t lds_bytes = ((size_t)fs * (fs + 1) + 2 * (size_t)fs) * sizeof(double);
-    hipMemset(dY, 0, (size_t)F * fs * nsp * 8);
-    hipMemset(dz, 0, (size_t)F * fs * 8);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k_s1_elim), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    LAUNCH_LDS(k_s1_elim, nown, 1, S1_TPB, lds_bytes, 0, dA, n, dg, dfc, fs, dsc, ns, nsp, dL, dY, dz, dst, fbase);
-    const size_t ybytes = ((size_t)fs * (fs + 1) + (size_t)S1_YC * fs) * sizeof(double);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k_s1_elim_y), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ybytes);
-    LAUNCH_LDS(k_s1_elim_y, nown, (ns + 1 + S1_YC - 1) / S1_YC, S1_TPB, ybytes, 0, dA, n, dg, dfc, fs, dsc, ns, nsp, dL, dY, dz, fbase);
-    { int nt = (ns + S1_T - 1) / S1_T; LAUNCH(k_s1_syrk, nt, nt, 256, 0, dY, F * fs, ns, nsp, dT, d1); }
-    LAUNCH(k_s1_schur_sub, ns, 1, S1_TPB, 0, dA, n, dg, dsc, ns, dT, dY, nsp, dz, F * fs, dS, dh);
-    chol_panels(dS, ns, dD, dst);
-    LAUNCH(k_s1_tri_solve, 1, 1, S1_CHOL_TPB, 0, dS, ns, dD, dh, dds);
-    LAUNCH(k_s1_back, nown, 1, S1_TPB, 0, dfc, fs, dsc, ns, nsp, dL, dY, dz, dds, dout, fbase, scatter_shared);
+    const S1Arrow a{dA, n, dg, dfc, F, fs, dsc, ns, nsp, d1, dL, dY, dz, dT, dS, dh, dD, dds, dst, fbase, nown};
+    s1_arrow_reduce(a, 0);
+    s1_arrow_solve(a, dout, false, scatter_shared, 0);
     return pr.finish();
 }
 

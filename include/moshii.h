@@ -75,7 +75,7 @@ const char* moshii_last_error(void);
  * check moshii_version() >= 101 before filling a moshii_stagei_desc declared from this header, and zero the struct first.
  * 102: moshii_solve_opts grew by the joint-angle term.  103: moshii_lbs_forward_shape_*.  104: moshii_model_set_faces,
  * moshii_vertex_normals_*, moshii_virtual_markers_* (new calls only: no struct changed).  105: moshii_surface_distance_*,
- * moshii_marker_surface_distance_* (new calls only). */
+ * moshii_marker_surface_distance_* (new calls only).  106: moshii_joints_* (new calls only). */
 int  moshii_version(void);
 /* first 16 hex digits of the SHA-256 over the sources this binary was compiled from (python -m moshpp_amd.build computes the same
  * over the tree: a stale binary is detectable); "unknown" for a build outside build.py */
@@ -227,6 +227,32 @@ int moshii_marker_surface_distance_f32(moshii_model_t m, int32_t F, const float*
 int moshii_marker_surface_distance_f64(moshii_model_t m, int32_t F, const double* pose, const double* trans, const double* shape /* or NULL */,
                                        int32_t N, const double* points, double* dist, int32_t* face /* or NULL */, int32_t* part /* or NULL */,
                                        double* nearest /* or NULL */, uint32_t flags, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Posed joints and world joint rotations of solved frames (version 106): the skeleton animation a Stage-II result is.
+ * ------------------------------------------------------------------------------------------- */
+
+/* The reference's J_transformed / Jtr and the rotation part of A_global (src/moshpp/models/smpl_fast_derivatives.py:218-229), for F
+ * frames at once: forward kinematics alone, no vertex is touched.
+ *   pose[F][NP], trans[F][3]   exactly what the matching moshii_lbs_forward[_shape]_* call takes (pose variables: the hand-PCA map is
+ *                              applied here too)
+ *   shape[F][nshape]           as there: NULL is the plain call; non-null without a declared block is MOSHII_ERR_ARG; the coefficients
+ *                              are an offset on the frozen betas and move the joints, J_f = J + JS . shape[f]
+ *   joints[F][K][3]            world position of every joint, translation included
+ *   rot[F][K][3][3]            world rotation of every joint, row major                                           (or NULL)
+ * so that the exported vertex v is sum_k w_vk (rot[f][k] (v_posed - J_f[k]) + joints[f][k]).  The local rotations are evaluated as the
+ * f64 export evaluates them (series below |r|^2 < 1e-6), so joints and exported vertices describe the same body.
+ * _f32 takes and returns f32 but computes in f64 and rounds once on the store: every stored value of _f32 is the f32 rounding of what
+ * _f64 stores for the same f32 inputs.
+ * One wavefront per frame, one lane per joint, the chain walked level by level across lanes.  Buffers host or
+ * device per flags; asynchronous on `stream` with MOSHII_BUFFERS_DEVICE.  64-bit addressing throughout: any F.  The call needs no
+ * faces and writes nothing on the handle: unlike the exports above it may run while an export of the same handle is in flight on
+ * another stream.  A null joints, a negative F, a call before moshii_model_set_betas: MOSHII_ERR_ARG, moshii_last_error names the
+ * fault.  F == 0: MOSHII_OK, nothing launched. */
+int moshii_joints_f32(moshii_model_t m, int32_t F, const float* pose, const float* trans, const float* shape /* or NULL */,
+                      float* joints, float* rot /* or NULL */, uint32_t flags, void* stream);
+int moshii_joints_f64(moshii_model_t m, int32_t F, const double* pose, const double* trans, const double* shape /* or NULL */,
+                      double* joints, double* rot /* or NULL */, uint32_t flags, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Pose prior. Replaces create_gmm_body_prior / MaxMixtureComplete
@@ -463,7 +489,9 @@ typedef struct moshii_stagei_desc {
 int moshii_stagei_solve(moshii_model_t m, moshii_prior_t prior /* may be NULL */, const moshii_stagei_desc* desc, void* stream);
 
 /* Introspection for benchmarks and tests: name, dynamic-LDS bytes and workgroup size of the kernel the last moshii_chain_solve or
- * moshii_vertex_normals_* call launched ("k_vn_lds", "k_vn_gather<float>", "k_vn_gather<double>" for the latter). */
+ * moshii_vertex_normals_* call launched ("k_vn_lds", "k_vn_gather<float>", "k_vn_gather<double>" for the latter), or the last
+ * moshii_joints_* call: "k_joints<float>", "k_joints<double>", "k_joints_shape<float>", "k_joints_shape<double>" (the last two with a
+ * shape row). */
 int moshii_last_launch_info(char* kernel_name, int32_t name_cap, int32_t* lds_bytes, int32_t* block_threads);
 
 #ifdef __cplusplus

@@ -105,6 +105,8 @@ EXPORTS = {
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     'moshii_marker_surface_distance_f64': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    'moshii_joints_f32': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    'moshii_joints_f64': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     'moshii_prior_create': (C.c_int, [C.c_int32, C.c_int32, _c_double_p, _c_double_p, _c_double_p, C.POINTER(C.c_void_p)]),
     'moshii_prior_destroy': (C.c_int, [C.c_void_p]),
     'moshii_attach_create': (C.c_int, [C.c_void_p, C.c_int32, _c_int_p, _c_double_p, C.POINTER(C.c_void_p)]),
@@ -244,7 +246,8 @@ class Model:
         if hasattr(J_regressor, 'toarray'):
             J_regressor = J_regressor.toarray()
         J_regressor = _f64(J_regressor)
-        posedirs = _f64(posedirs).reshape(V, 3, -1)
+        posedirs = _f64(posedirs)
+        posedirs = posedirs.reshape(V, 3, posedirs.size // max(3 * V, 1))   # (a one-joint model has no pose features: zero columns)
         weights = _f64(weights)
         assert posedirs.shape[2] == 9 * (K - 1), (posedirs.shape, K)
         assert weights.shape == (V, K) and J_regressor.shape == (K, V)
@@ -472,6 +475,36 @@ class Model:
             raise ValueError('marker_surface_distance_device: shape_ptr given, but the model has no free shape block (set_free_shape)')
         fn = load().moshii_marker_surface_distance_f32 if f32 else load().moshii_marker_surface_distance_f64
         check(fn(self.handle, F, pose_ptr, trans_ptr, shape_ptr, N, points_ptr, dist_ptr, face_ptr, part_ptr, nearest_ptr, BUFFERS_DEVICE, stream))
+
+    # ---- the skeleton: posed joints and world joint rotations ----
+    def posed_joints(self, pose, trans, shape=None, dtype=np.float64, return_rotations=False):
+        """joints[F, K, 3]: the world position of every joint (translation included) for pose variables pose[F, NP], trans[F, 3] (host
+        arrays) -- forward kinematics alone, the reference's J_transformed.  shape as in lbs_forward (the joints move with the
+        coefficients).  return_rotations: (joints, rot[F, K, 3, 3]), the world rotation of every joint (A_global's rotation part).
+        float32 computes in float64 and rounds once.  joints() stays the REST joints."""
+        if dtype not in (np.float64, np.float32):
+            raise ValueError(f'posed_joints: dtype must be numpy float64 or float32, not {dtype!r}')
+        pose = np.ascontiguousarray(np.atleast_2d(pose), dtype=dtype)
+        trans = np.ascontiguousarray(np.atleast_2d(trans), dtype=dtype)
+        F = pose.shape[0]
+        if pose.shape != (F, self.NP) or trans.shape != (F, 3):
+            raise ValueError(f'posed_joints: pose / trans must be [F, {self.NP}] / [F, 3], got {pose.shape} / {trans.shape}')
+        if shape is not None:
+            shape = self._check_shape_rows(shape, F, dtype)
+        out = np.zeros((F, self.K, 3), dtype=dtype)
+        rot = np.zeros((F, self.K, 3, 3), dtype=dtype) if return_rotations else None
+        fn = load().moshii_joints_f64 if dtype == np.float64 else load().moshii_joints_f32
+        check(fn(self.handle, F, pose.ctypes.data, trans.ctypes.data, shape.ctypes.data if shape is not None else None, out.ctypes.data,
+                 rot.ctypes.data if return_rotations else None, BUFFERS_HOST, None))
+        return (out, rot) if return_rotations else out
+
+    def posed_joints_device(self, F, pose_ptr, trans_ptr, out_ptr, rot_ptr=None, stream=None, f32=True, shape_ptr=None):
+        """Device buffers (f32: float, else double) for pose / trans / shape / joints[F][K][3] / rot[F][K][3][3]; asynchronous on
+        `stream`."""
+        if shape_ptr is not None and int(getattr(self, 'n_free_shape', 0)) <= 0:
+            raise ValueError('posed_joints_device: shape_ptr given, but the model has no free shape block (set_free_shape)')
+        fn = load().moshii_joints_f32 if f32 else load().moshii_joints_f64
+        check(fn(self.handle, F, pose_ptr, trans_ptr, shape_ptr, out_ptr, rot_ptr, BUFFERS_DEVICE, stream))
 
     def lbs_forward_with_normals(self, pose, trans, dtype=np.float32, shape=None):
         """(verts, normals), both [F, V, 3]: the export into a device buffer, the normals from that buffer, two copies back -- the

@@ -233,6 +233,17 @@ class StageIISolver:
                 raise KeyError(f"StageIISolver.vertices: the result has no '{k}'")
         return self.dev.lbs_forward(out['pose'], out['trans'], dtype=dtype, shape=out['shape'] if self.n_shape else None)
 
+    def joints(self, out, dtype=np.float64, return_rotations=False):
+        """joints[F, K, 3] of a solve() result: the world position of every joint on every solved frame (translation included; the
+        reference's J_transformed) -- on the solver's own model handle, hand PCA and, with a free block, the per-frame coefficients
+        out['shape'] included, so the skeleton is the one the solve moved.  return_rotations: (joints, rot[F, K, 3, 3]), the world
+        rotation of every joint.  Rows of unsolved frames (status 1) hold whatever pose the chain carried there."""
+        for k in ('pose', 'trans') + (('shape',) if self.n_shape else ()):
+            if k not in out:
+                raise KeyError(f"StageIISolver.joints: the result has no '{k}'")
+        return self.dev.posed_joints(out['pose'], out['trans'], shape=out['shape'] if self.n_shape else None, dtype=dtype,
+                                     return_rotations=return_rotations)
+
     def virtual_markers(self, out, vids, dist, dtype=np.float32, return_normals=False):
         """markers[F, M, 3] of a solve() result: vertex vids[i] of every solved frame's mesh + dist[i] x its vertex normal (the
         reference's marker placement rule, chmosh.py:57-67, on every frame) -- on the solver's own handle, the meshes stay on the

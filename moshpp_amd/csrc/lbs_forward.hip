@@ -1334,6 +1334,119 @@ __global__ __launch_bounds__(256) void k_sd_finish(int V, long long total, int N
     }
 }
 
+// ---- posed joints and world joint rotations of solved frames (moshii_joints_*) ----------------------------------------------------
+// The reference's J_transformed / A_global (src/moshpp/models/smpl_fast_derivatives.py:218-229) for F frames: the kinematic chain
+// alone, no vertex touched.  K <= 64 joints are exactly one wavefront: ONE WAVE PER FRAME, LANE k = JOINT k, JT_WAVES frames a
+// workgroup, no loop over frames.  Everything of a frame lives in the wave's registers, in f64 whatever T is (T = float converts on
+// the loads and rounds once on the stores):
+//   fullpose   the lane's three components: the pose variables themselves (body joints) or hands_mean + sum_i pose_hand[i] comps[i][h]
+//              over each column's non-zero rows col_lo .. col_hi, the rows of the lane's three columns fetched JT_ROWS at a time
+//   Rodrigues  the evaluation of k_lbs_f64 (moshii_api.hip), term for term: joints and exported vertices describe the same body
+//   joints     SH: J_k + JS[k] . shape[f], summed in k_lbs_f64's order
+//   chain      level by level: at depth d the lanes of that depth take their parent's world rotation and position ACROSS LANES (twelve
+//              f64 shuffles a level, every lane taking part in each: the loop bound maxdepth is uniform) and form Rw = Rw_p . R,
+//              tw = Rw_p . (J_k - J_p) + tw_p in k_lbs_f64's order of operations.  No LDS, no barrier.
+// A wave's output is one contiguous run: lane k stores its 3 (and 9) values behind lane k - 1's.  Waves behind the last frame and lanes
+// behind the last joint shadow frame F - 1 / joint K - 1 and store nothing.  All addressing is 64-bit.
+#define JT_WAVES 4
+#define JT_ROWS 8              // hand-component rows a lane fetches in one batch
+template <class T, bool SH>
+__global__ __launch_bounds__(64 * JT_WAVES) void k_joints(ModelDev md, int F, const T* __restrict__ pose, const T* __restrict__ trans,
+                                                          const T* __restrict__ shape, T* __restrict__ joints, T* __restrict__ rot) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, K = md.K;
+    const long long fw = (long long)blockIdx.x * JT_WAVES + wv;
+    const size_t f = (size_t)(fw < F ? fw : F - 1);
+    const int k = lane < K ? lane : K - 1;
+    const bool act = lane < K && fw < F;
+    const int p = md.parents[k], dk = lane < K ? md.depth[k] : -1;
+    const T* ps = pose + f * md.NP;
+    const int bd = md.body_dof, nhf = md.nhand_full;
+    double rv[3], Jk[3];
+    if (3 * k < bd) {                // (body_dof is a multiple of three: a joint's components are pose variables or hand dofs together)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) rv[i] = (double)ps[3 * k + i];
+    } else {
+        // component i sums its own rows lo[i] .. hi[i] in ascending order; the rows of all three are fetched together, JT_ROWS at a time (one
+        // round trip a batch instead of one a row and component: what a wave waits for here is latency)
+        const int h = 3 * k - bd;
+        int lo[3], hi[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { lo[i] = md.col_lo[h + i]; hi[i] = md.col_hi[h + i]; rv[i] = md.hands_mean[h + i]; }
+        const int c0 = min(min(lo[0], lo[1]), lo[2]), c1 = max(max(hi[0], hi[1]), hi[2]);
+        for (int c = c0; c < c1; c += JT_ROWS) {
+            double pu[JT_ROWS], cm[JT_ROWS][3];
+#pragma unroll
+            for (int u = 0; u < JT_ROWS; ++u) {
+                const int cc = min(c + u, c1 - 1);
+                pu[u] = (double)ps[bd + cc];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) cm[u][i] = md.comps[(size_t)cc * nhf + h + i];
+            }
+#pragma unroll
+            for (int u = 0; u < JT_ROWS; ++u)
+#pragma unroll
+                for (int i = 0; i < 3; ++i)
+                    if (c + u >= lo[i] && c + u < hi[i]) rv[i] += pu[u] * cm[u][i];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const int d = 3 * k + i;
+        double s = md.J[d];
+        if (SH) {
+            const int E = md.nshape;
+            const T* cf = shape + f * E;
+#pragma unroll 4
+            for (int e = 0; e < E; ++e) s += md.JS[((size_t)k * E + e) * 3 + i] * (double)cf[e];
+        }
+        Jk[i] = s;
+    }
+    double R[9];
+    {
+        const double x = rv[0], y = rv[1], z = rv[2];
+        const double t2 = x * x + y * y + z * z;
+        double a, b;
+        if (t2 < 1e-6) { a = 1.0 - t2 / 6.0 + t2 * t2 / 120.0; b = 0.5 - t2 / 24.0 + t2 * t2 / 720.0; }
+        else { const double t = sqrt(t2); a = sin(t) / t; b = (1.0 - cos(t)) / t2; }
+        const double K2[9] = {x * x - t2, x * y, x * z, x * y, y * y - t2, y * z, x * z, y * z, z * z - t2};
+        const double Km[9] = {0.0, -z, y, z, 0.0, -x, -y, x, 0.0};
+#pragma unroll
+        for (int e = 0; e < 9; ++e) R[e] = ((e == 0 || e == 4 || e == 8) ? 1.0 : 0.0) + a * Km[e] + b * K2[e];
+    }
+    // the root's world transform is its own; every other lane's is formed at its depth
+    double Rw[9], tw[3], dJ[3];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) Rw[e] = R[e];
+    const int src = p > 0 ? p : 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { tw[i] = Jk[i]; dJ[i] = Jk[i] - __shfl(Jk[i], src); }
+    for (int d = 1; d <= md.maxdepth; ++d) {
+        double pr[9], pt[3];
+#pragma unroll
+        for (int e = 0; e < 9; ++e) pr[e] = __shfl(Rw[e], src);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) pt[i] = __shfl(tw[i], src);
+        if (dk == d) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) Rw[i * 3 + j] = pr[i * 3 + 0] * R[0 * 3 + j] + pr[i * 3 + 1] * R[1 * 3 + j] + pr[i * 3 + 2] * R[2 * 3 + j];
+                tw[i] = pr[i * 3 + 0] * dJ[0] + pr[i * 3 + 1] * dJ[1] + pr[i * 3 + 2] * dJ[2] + pt[i];
+            }
+        }
+    }
+    if (!act) return;
+    const T* tr = trans + f * 3;
+    T* oj = joints + (f * K + k) * 3;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) oj[i] = (T)(tw[i] + (double)tr[i]);
+    if (rot != nullptr) {
+        T* orot = rot + (f * K + k) * 9;
+#pragma unroll
+        for (int e = 0; e < 9; ++e) orot[e] = (T)Rw[e];
+    }
+}
+
 }  // namespace
 
 static void free_ptr(void* p) { if (p) hipFree(p); }
@@ -1823,4 +1936,25 @@ extern "C" hipError_t moshii_launch_surface_distance(hipStream_t stream, int V, 
     }
     if (e != hipSuccess) return e;
     return sd_launch_finish<float>(stream, V, total, N, (const float*)verts, (const float*)points, tris, w16, rows, pairs, (float*)dist, face, part, (float*)nearest);
+}
+
+// ---- posed joints / world joint rotations: launch (the checks live in moshii_api.hip) ----
+// One wave per frame, JT_WAVES frames a workgroup; needs nothing on the handle beyond the model arrays in *md.  rot may be null.
+// *which: the kernel's name for moshii_last_launch_info, *threads its workgroup size.
+template <class T>
+static hipError_t joints_launch(hipStream_t stream, const ModelDev& md, int F, const T* pose, const T* trans, const T* shape, T* joints, T* rot) {
+    const dim3 grid((unsigned)(((long long)F + JT_WAVES - 1) / JT_WAVES));
+    if (shape) hipLaunchKernelGGL((k_joints<T, true>), grid, dim3(64 * JT_WAVES), 0, stream, md, F, pose, trans, shape, joints, rot);
+    else hipLaunchKernelGGL((k_joints<T, false>), grid, dim3(64 * JT_WAVES), 0, stream, md, F, pose, trans, shape, joints, rot);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t moshii_launch_joints(hipStream_t stream, const ModelDev* md, int F, int f64, const void* pose, const void* trans,
+                                           const void* shape, void* joints, void* rot, const char** which, int* threads) {
+    if (which) *which = "";
+    if (threads) *threads = 64 * JT_WAVES;
+    if (F <= 0) return hipSuccess;
+    if (which) *which = f64 ? (shape ? "k_joints_shape<double>" : "k_joints<double>") : (shape ? "k_joints_shape<float>" : "k_joints<float>");
+    if (f64) return joints_launch<double>(stream, *md, F, (const double*)pose, (const double*)trans, (const double*)shape, (double*)joints, (double*)rot);
+    return joints_launch<float>(stream, *md, F, (const float*)pose, (const float*)trans, (const float*)shape, (float*)joints, (float*)rot);
 }

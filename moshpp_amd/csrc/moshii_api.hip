@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -31,6 +32,8 @@ extern "C" hipError_t moshii_launch_surface_distance(hipStream_t stream, int V, 
                                                      const void* points, const unsigned* tris, int w16, const unsigned* rows,
                                                      const unsigned* pairs, void* dist, int* face, int* part, void* nearest,
                                                      const char** which, int* lds_bytes, int* threads);
+extern "C" hipError_t moshii_launch_joints(hipStream_t stream, const ModelDev* md, int F, int f64, const void* pose, const void* trans,
+                                           const void* shape, void* joints, void* rot, const char** which, int* threads);
 
 namespace {
 
@@ -371,6 +374,11 @@ ChainLayout make_layout(const moshii_model_s* m, int Mmax, int Nvmax, int NWmax,
 }
 
 struct LaunchInfo { std::string name; int lds = 0; int threads = 0; } g_last;
+std::mutex g_last_mutex;   // (moshii_joints_* may run on several host threads at once)
+void note_launch(const std::string& name, int lds, int threads) {
+    std::lock_guard<std::mutex> hold(g_last_mutex);
+    g_last.name = name; g_last.lds = lds; g_last.threads = threads;
+}
 
 }  // namespace
 
@@ -378,7 +386,7 @@ struct LaunchInfo { std::string name; int lds = 0; int threads = 0; } g_last;
 extern "C" {
 
 const char* moshii_last_error(void) { return g_err.c_str(); }
-int moshii_version(void) { return 105; }   // 101: moshii_stagei_desc grew by init_sq; 102: moshii_solve_opts by the joint-angle term; 103: moshii_lbs_forward_shape_*; 104: moshii_model_set_faces, moshii_vertex_normals_*, moshii_virtual_markers_*; 105: moshii_surface_distance_*, moshii_marker_surface_distance_* (include/moshii.h)
+int moshii_version(void) { return 106; }   // 101: moshii_stagei_desc grew by init_sq; 102: moshii_solve_opts by the joint-angle term; 103: moshii_lbs_forward_shape_*; 104: moshii_model_set_faces, moshii_vertex_normals_*, moshii_virtual_markers_*; 105: moshii_surface_distance_*, moshii_marker_surface_distance_*; 106: moshii_joints_* (include/moshii.h)
 #ifndef MOSHII_SRC_HASH
 #define MOSHII_SRC_HASH "unknown"
 #endif
@@ -712,7 +720,7 @@ static int vertex_normals_impl(moshii_model_t m, int32_t F, const T* verts, T* n
     const char* which = "";
     int lds = 0, threads = 0;
     HIP_TRY(moshii_launch_vertex_normals(stream, m->V, F, sizeof(T) == 8, d_in, d_out, m->d_vn_rows, m->d_vn_pairs, m->vn_w16, &which, &lds, &threads));
-    g_last.name = which; g_last.lds = lds; g_last.threads = threads;
+    note_launch(which, lds, threads);
     if (!dev) {
         HIP_TRY(hipStreamSynchronize(stream));
         HIP_TRY(hipMemcpy(normals, t_out, n * sizeof(T), hipMemcpyDeviceToHost));
@@ -833,7 +841,7 @@ static int surface_distance_launch(moshii_model_t m, int F, const T* d_verts, in
     int lds = 0, threads = 0;
     HIP_TRY(moshii_launch_surface_distance(stream, m->V, m->n_faces, F, N, sizeof(T) == 8, d_verts, d_points, m->d_sd_tris, m->vn_w16, m->d_vn_rows,
                                            m->d_vn_pairs, d_dist, d_face ? d_face : d_win, d_part, d_near, &which, &lds, &threads));
-    g_last.name = which; g_last.lds = lds; g_last.threads = threads;
+    note_launch(which, lds, threads);
     return MOSHII_OK;
 }
 
@@ -960,6 +968,62 @@ int moshii_marker_surface_distance_f32(moshii_model_t m, int32_t F, const float*
 int moshii_marker_surface_distance_f64(moshii_model_t m, int32_t F, const double* pose, const double* trans, const double* shape, int32_t N,
                                        const double* points, double* dist, int32_t* face, int32_t* part, double* nearest, uint32_t flags, void* stream) {
     return marker_surface_distance_impl(m, F, pose, trans, shape, N, points, dist, face, part, nearest, flags, stream, "moshii_marker_surface_distance_f64");
+}
+
+}  // extern "C"
+
+// ---- posed joints and world joint rotations (version 106) ----
+// Nothing of the handle is written: no scratch, no f32 copy, no faces -- the kernel reads the model arrays and the caller's buffers, so
+// the call may run beside an export of the same handle on another stream.
+template <class T>
+static int joints_impl(moshii_model_t m, int32_t F, const T* pose, const T* trans, const T* shape, T* joints, T* rot, uint32_t flags,
+                       void* stream_, const char* name) {
+    if (!m) return fail(MOSHII_ERR_ARG, std::string(name) + ": null model");
+    if (F < 0) return fail(MOSHII_ERR_ARG, std::string(name) + ": negative F");
+    if (!joints) return fail(MOSHII_ERR_ARG, std::string(name) + ": joints is null");
+    if (!m->betas_set) return fail(MOSHII_ERR_ARG, std::string(name) + ": moshii_model_set_betas has not been called");
+    if (shape && m->nshape == 0) return fail(MOSHII_ERR_ARG, "shape coefficients without a block: call moshii_model_set_free_shape first");
+    if (F == 0) return MOSHII_OK;
+    if (!pose || !trans) return fail(MOSHII_ERR_ARG, std::string(name) + ": pose or trans is null");
+    hipStream_t stream = (hipStream_t)stream_;
+    const bool dev = (flags & MOSHII_BUFFERS_DEVICE) != 0;
+    const size_t nj = (size_t)F * m->K * 3;
+    const T *d_pose = pose, *d_trans = trans, *d_shape = shape;
+    T *d_joints = joints, *d_rot = rot;
+    DevTemps temps;
+    if (!dev) {
+        T *t_pose = nullptr, *t_trans = nullptr, *t_shape = nullptr, *t_joints = nullptr, *t_rot = nullptr;
+        int rc = dev_upload(pose, (size_t)F * m->NP, &t_pose); temps.keep(t_pose);
+        if (rc) return rc;
+        rc = dev_upload(trans, (size_t)F * 3, &t_trans); temps.keep(t_trans);
+        if (rc) return rc;
+        if (shape) { rc = dev_upload(shape, (size_t)F * m->nshape, &t_shape); temps.keep(t_shape); if (rc) return rc; }
+        HIP_TRY(hipMalloc((void**)&t_joints, nj * sizeof(T))); temps.keep(t_joints);
+        if (rot) { HIP_TRY(hipMalloc((void**)&t_rot, nj * 3 * sizeof(T))); temps.keep(t_rot); }
+        d_pose = t_pose; d_trans = t_trans; d_shape = t_shape; d_joints = t_joints; d_rot = t_rot;
+    }
+    const ModelDev md = m->dev();
+    const char* which = "";
+    int threads = 0;
+    HIP_TRY(moshii_launch_joints(stream, &md, F, sizeof(T) == 8, d_pose, d_trans, d_shape, d_joints, d_rot, &which, &threads));
+    note_launch(which, 0, threads);
+    if (!dev) {
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemcpy(joints, d_joints, nj * sizeof(T), hipMemcpyDeviceToHost));
+        if (rot) HIP_TRY(hipMemcpy(rot, d_rot, nj * 3 * sizeof(T), hipMemcpyDeviceToHost));
+    }
+    return MOSHII_OK;
+}
+
+extern "C" {
+
+int moshii_joints_f32(moshii_model_t m, int32_t F, const float* pose, const float* trans, const float* shape, float* joints, float* rot,
+                      uint32_t flags, void* stream) {
+    return joints_impl(m, F, pose, trans, shape, joints, rot, flags, stream, "moshii_joints_f32");
+}
+int moshii_joints_f64(moshii_model_t m, int32_t F, const double* pose, const double* trans, const double* shape, double* joints, double* rot,
+                      uint32_t flags, void* stream) {
+    return joints_impl(m, F, pose, trans, shape, joints, rot, flags, stream, "moshii_joints_f64");
 }
 
 int moshii_prior_create(int32_t G, int32_t npose, const double* means, const double* chols, const double* weights,
@@ -1332,9 +1396,8 @@ int prepare_launch(moshii_model_t m, moshii_prior_t prior, const moshii_solve_op
 
 int launch_chains(const LaunchCfg& cfg, int n, const ChainDev* d_chains, hipStream_t stream) {
     HIP_TRY(moshii_launch_chain_solve(cfg.nblk, cfg.xt, n, cfg.lds_bytes, stream, d_chains, &cfg.md, &cfg.pd, &cfg.od, &cfg.ly, cfg.coop_g));
-    g_last.name = "k_chain_solve<" + std::to_string(cfg.nblk) + ",1" + (cfg.xt ? ",xt" : "") +
-                  (cfg.coop_g > 0 ? ",coop" + std::to_string(cfg.coop_g) : "") + ">";
-    g_last.lds = (int)cfg.lds_bytes; g_last.threads = MOSHII_TPB;
+    note_launch("k_chain_solve<" + std::to_string(cfg.nblk) + ",1" + (cfg.xt ? ",xt" : "") +
+                (cfg.coop_g > 0 ? ",coop" + std::to_string(cfg.coop_g) : "") + ">", (int)cfg.lds_bytes, MOSHII_TPB);
     return MOSHII_OK;
 }
 
@@ -1934,6 +1997,7 @@ int moshii_stagei_solve(moshii_model_t m, moshii_prior_t prior, const moshii_sta
 }
 
 int moshii_last_launch_info(char* kernel_name, int32_t name_cap, int32_t* lds_bytes, int32_t* block_threads) {
+    std::lock_guard<std::mutex> hold(g_last_mutex);
     if (kernel_name && name_cap > 0) { strncpy(kernel_name, g_last.name.c_str(), name_cap - 1); kernel_name[name_cap - 1] = 0; }
     if (lds_bytes) *lds_bytes = g_last.lds;
     if (block_threads) *block_threads = g_last.threads;

@@ -553,3 +553,47 @@ def stageii_marker_skin_distance(stageii_data_or_fname, surface_model=None, fram
     from .chmosh import skin_distance_summary
     return dict(labels=labels, distance=res.distance, face=res.face, part=res.part, frame_ids=np.asarray(ids),
                 summary=skin_distance_summary(res.distance, labels))
+
+
+def _stageii_joints_plan(pkl, frame_ids, out_fname):
+    """Every refusal of stageii_joints that needs no model file and no device; (plan, frame rate | None)."""
+    plan = _stageii_vertices_plan(pkl, frame_ids)
+    rate = pkl['stageii_debug_details'].get('mocap_frame_rate')
+    if out_fname is not None:
+        if not str(out_fname).endswith('.npz'):
+            raise ValueError(f'stageii_joints: out_fname must end in .npz: {out_fname}')
+        if rate is None:
+            raise KeyError("stageii_joints: the Stage-II data stores no frame rate (stageii_debug_details['mocap_frame_rate']) "
+                           "to write the file with")
+        if osp.exists(str(out_fname)):
+            raise FileExistsError(f'stageii_joints: {out_fname} exists; remove it or choose another name')
+    return plan, None if rate is None else float(rate)
+
+
+def stageii_joints(stageii_data_or_fname, surface_model=None, frame_ids=None, dtype=np.float64, return_rotations=False, out_fname=None):
+    """The skeleton animation a Stage-II result (pickle file name or dict) is: dict(joints[T, K, 3] world joint positions with the
+    translation, rotations[T, K, 3, 3] world joint rotations (with return_rotations), parents[K], frame_ids, mocap_frame_rate (None
+    where the result stores none), surface_model_type) -- the reference's J_transformed / A_global (smpl_fast_derivatives.py:218-229)
+    from the kinematic chain itself, not regressed from posed vertices: right with pose correctives active, and following the per-frame
+    expression / DMPL coefficients where the solve freed them.  For retargeting, MPJPE-style evaluation, contact and velocity analysis,
+    skeleton viewers.
+
+    surface_model / frame_ids: as in stageii_vertices.  dtype float64 or float32 (computed in float64, rounded once).
+    out_fname: a '.npz' that receives the same entries; its directory is created, an existing file is refused (before any work)."""
+    pkl = _stageii_load(stageii_data_or_fname)
+    plan, rate = _stageii_joints_plan(pkl, frame_ids, out_fname)
+    sm, mp, kind, start, count, ids = plan
+    surface_model, shapedirs, b, fullpose, trans, coef = _stageii_export_inputs(pkl, plan, surface_model)
+    dev = _stageii_device(surface_model, shapedirs, b, kind, start, count)
+    try:
+        res = dev.posed_joints(fullpose, trans, shape=coef, dtype=dtype, return_rotations=return_rotations)
+    finally:
+        dev.close()
+    out = dict(joints=res[0] if return_rotations else res)
+    if return_rotations:
+        out['rotations'] = res[1]
+    out.update(parents=np.asarray(surface_model.parents, dtype=np.int32), frame_ids=np.asarray(ids), mocap_frame_rate=rate,
+               surface_model_type=sm['type'])
+    if out_fname is not None:
+        np.savez(_makepath(str(out_fname)), **out)
+    return out

@@ -8,7 +8,10 @@ and through the gather kernel, export + normals, and the virtual-marker call for
 fraction of 8 TB/s under F V 24 B + the face table.
 --surface-distance [F] [reps] [--model NAME]: the signed marker-to-skin distance of 53 points a frame on the same body: the staged f32
 kernel, the gather kernel in f32 and f64, and the fused entry (export + distance, meshes in the handle's scratch) -- ms, point-triangle
-tests per second and the share of the f32 vector peak the tests' arithmetic comes to."""
+tests per second and the share of the f32 vector peak the tests' arithmetic comes to.
+--joints [F] [--model NAME]: posed joints and world joint rotations (moshii_joints_*) of F frames (default 4000, smplh) on device
+buffers, f32 and f64, with and without the rotations: HIP events around one call, median of 20 after 3 warm-ups, the launch shape and
+the bytes moved; beside it moshii_lbs_forward_f32 on the same frames, timed the same way."""
 import ctypes as C, sys, time
 import numpy as np
 sys.path.insert(0, '.')
@@ -186,6 +189,73 @@ def surface_distance_bench(argv):
           f'|d| median {float(dist.abs().median()) * 1e3:.2f} mm, {float((dist < 0).float().mean()) * 100:.1f} % inside')
 
 
+def joints_bench(argv):
+    import os
+    import torch
+    from moshpp_amd import synth, workload
+    mt = 'smplh'
+    if '--model' in argv:
+        i = argv.index('--model')
+        mt = argv[i + 1]
+        del argv[i:i + 2]
+    F = int(argv[0]) if len(argv) > 0 else 4000
+    job = workload.make_job(mt, 8, {'smplh': 53, 'smpl': 41, 'smplx': 89, 'mano': 33}[mt], seed=1000, optimize_fingers=(mt == 'mano'),
+                            dd=synth.synth_model(mt, seed=1000))
+    solver = workload.make_solver(job)
+    model, sm = solver.dev, job['sm']
+    K, V, NP = sm.K, sm.V, sm.NP
+    dev = torch.device('cuda', 0)
+    rng = np.random.default_rng(0)
+    pose_h, trans_h = rng.normal(0, 0.3, (F, NP)), rng.normal(0, 1, (F, 3))
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def timed(fn):                      # HIP events around ONE call, median of 20 after 3 warm-ups
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(20):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) * 1e3)
+        return np.median(ts), min(ts), max(ts)
+
+    print(f'{mt}: K = {K} joints, NP = {NP} pose variables, V = {V}, F = {F} frames, device buffers, HIP events around one call, median of 20 '
+          f'calls after 3 warm-ups (fastest .. slowest); library {os.path.basename(capi.LIB_PATH)} {capi.load().moshii_source_hash().decode()}')
+    keep = {}
+    for dt, tdt in ((np.float32, torch.float32), (np.float64, torch.float64)):
+        isz = np.dtype(dt).itemsize
+        pose = torch.from_numpy(pose_h.astype(dt)).to(dev)
+        trans = torch.from_numpy(trans_h.astype(dt)).to(dev)
+        joints = torch.empty((F, K, 3), dtype=tdt, device=dev)
+        rot = torch.empty((F, K, 3, 3), dtype=tdt, device=dev)
+        for with_rot in (True, False):
+            fn = lambda: model.posed_joints_device(F, pose.data_ptr(), trans.data_ptr(), joints.data_ptr(), rot.data_ptr() if with_rot else None,
+                                                   stream, f32=dt == np.float32)
+            med, lo, hi = timed(fn)
+            kname, klds, kthreads = capi.last_launch_info()
+            nbytes = F * (NP + 3) * isz + F * K * (12 if with_rot else 3) * isz
+            print(f'  {kname:18s} {"joints + rotations" if with_rot else "joints alone":20s} {med:8.1f} us ({lo:.1f} .. {hi:.1f})   grid {(F + 3) // 4} x {kthreads} threads '
+                  f'(one wave a frame), {klds} B LDS; {nbytes / 1e6:.2f} MB moved (in {F * (NP + 3) * isz / 1e6:.2f}, out {(nbytes - F * (NP + 3) * isz) / 1e6:.2f}) '
+                  f'-> {nbytes / med / 1e3:.1f} GB/s')
+        keep[dt] = (pose, trans, joints.cpu().numpy(), rot.cpu().numpy())
+    pose, trans = (torch.from_numpy(a.astype(np.float32)).to(dev) for a in (pose_h, trans_h))
+    verts = torch.empty((F, V, 3), dtype=torch.float32, device=dev)
+    med, lo, hi = timed(lambda: model.lbs_forward_device(F, pose.data_ptr(), trans.data_ptr(), verts.data_ptr(), stream))
+    print(f'  for scale: moshii_lbs_forward_f32 on the same frames {med:8.1f} us ({lo:.1f} .. {hi:.1f}), {F * V * 12 / 1e6:.1f} MB out')
+    ref = model.posed_joints(pose_h[:2].astype(np.float32), trans_h[:2].astype(np.float32), dtype=np.float32)
+    print(f'  check: device-buffer joints vs the host-buffer call on 2 frames: max |diff| {np.abs(keep[np.float32][2][:2] - ref).max():.1e}; '
+          f'f32 vs f64 joints on all frames: max |diff| {np.abs(keep[np.float32][2] - keep[np.float64][2]).max():.1e} m')
+
+
+if '--joints' in sys.argv:
+    from moshpp_amd import capi
+    sys.argv.remove('--joints')
+    joints_bench(sys.argv[1:])
+    sys.exit(0)
 if '--surface-distance' in sys.argv:
     from moshpp_amd import capi
     sys.argv.remove('--surface-distance')

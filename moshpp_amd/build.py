@@ -17,7 +17,7 @@ EXTRA_FLAGS = {'chain_solve.hip': ['-mllvm', '-amdgpu-sched-strategy=iterative-i
                'lbs_forward.hip': ['-fno-slp-vectorize']}
 if os.environ.get('MOSHII_NO_ILP'):
     EXTRA_FLAGS = {}
-HEADERS = ['moshii_dev.h', 'solve_plan.h', 'stagei_plan.h', 'stagei_views.h', os.path.join('..', '..', 'include', 'moshii.h')]
+HEADERS = ['moshii_dev.h', 'dev_mem.h', 'export_plan.h', 'solve_plan.h', 'stagei_plan.h', 'stagei_views.h', os.path.join('..', '..', 'include', 'moshii.h')]
 OUT = os.path.join(HERE, 'libmoshii.so')
 LAST_BUILD_RAN_HIPCC = False   # set by build(): did this call compile anything?
 

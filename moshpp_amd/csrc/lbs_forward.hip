@@ -30,11 +30,13 @@
 // block; SMPL-X with 80 coefficients 386 us per 4000-frame export against 303 us without (profiles/lbs_shape_export.txt).
 #include "../../include/moshii.h"
 #include "moshii_dev.h"
+#include "dev_mem.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <cstdlib>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -1527,11 +1529,17 @@ extern "C" int moshii_lbs32_prepare(moshii_model_t m) {
     Lbs32Model* lm = (Lbs32Model*)moshii_internal_l32(m);
     const int Vp = (V + 63) & ~63;
     const int nfeat = 9 * (K - 1);
+    DevArena tmp;   // the reductions' buffers
+    // any failure frees the whole copy: the next call finds no v_shaped and builds it again, never over half of one
+    auto bad = [&](const char* what) {
+        moshii_lbs32_free(lm);
+        return moshii_internal_fail(MOSHII_ERR_HIP, (std::string("moshii_lbs32_prepare: device allocation failed: ") + what).c_str());
+    };
     if (!lm->v_shaped) {
-        if (hipMalloc((void**)&lm->v_shaped, (size_t)V * 3 * sizeof(float)) != hipSuccess) return MOSHII_ERR_HIP;
-        if (hipMalloc((void**)&lm->posedirs_t, (size_t)std::max(nfeat, 1) * 3 * Vp * sizeof(float)) != hipSuccess) return MOSHII_ERR_HIP;
-        if (hipMalloc((void**)&lm->weights, (size_t)K * Vp * sizeof(float)) != hipSuccess) return MOSHII_ERR_HIP;
-        if (hipMalloc((void**)&lm->J, (size_t)K * 3 * sizeof(float)) != hipSuccess) return MOSHII_ERR_HIP;
+        if (hipMalloc((void**)&lm->v_shaped, (size_t)V * 3 * sizeof(float)) != hipSuccess) return bad("v_shaped");
+        if (hipMalloc((void**)&lm->posedirs_t, (size_t)std::max(nfeat, 1) * 3 * Vp * sizeof(float)) != hipSuccess) return bad("posedirs_t");
+        if (hipMalloc((void**)&lm->weights, (size_t)K * Vp * sizeof(float)) != hipSuccess) return bad("weights");
+        if (hipMalloc((void**)&lm->J, (size_t)K * 3 * sizeof(float)) != hipSuccess) return bad("J");
         lm->Vp = Vp;
         hipLaunchKernelGGL(k_cvt_posedirs, dim3(2048), dim3(256), 0, 0, V, Vp, nfeat, moshii_internal_posedirs(m), lm->posedirs_t);
         hipLaunchKernelGGL(k_cvt_weights, dim3(512), dim3(256), 0, 0, V, Vp, K, moshii_internal_weights(m), lm->weights);
@@ -1585,12 +1593,11 @@ extern "C" int moshii_lbs32_prepare(moshii_model_t m) {
         }
         lm->NRM = NRM;
         if (ok) {
-            double* d_part = nullptr;
-            if (hipMalloc((void**)&d_part, 256 * sizeof(double)) != hipSuccess) return MOSHII_ERR_HIP;
+            double* d_part = tmp.alloc<double>(256);
+            if (!d_part) return bad("the reduction buffer");
             hipLaunchKernelGGL(k_absmax, dim3(256), dim3(256), 0, 0, (size_t)V * 3 * nfeat, moshii_internal_posedirs(m), d_part);
             double part[256];
-            if (hipMemcpy(part, d_part, sizeof(part), hipMemcpyDeviceToHost) != hipSuccess) return MOSHII_ERR_HIP;
-            hipFree(d_part);
+            if (hipMemcpy(part, d_part, sizeof(part), hipMemcpyDeviceToHost) != hipSuccess) return bad("the reduction buffer (copy)");
             double amax = 0.0;
             for (double p : part) amax = std::max(amax, p);
             // power-of-two scale that lifts the largest corrective to ~2^13: small entries stay normal in f16
@@ -1598,8 +1605,8 @@ extern "C" int moshii_lbs32_prepare(moshii_model_t m) {
             if (amax > 0.0) pscale = std::ldexp(1.0, 13 - (int)std::ceil(std::log2(amax)));
             lm->pscale = (float)pscale;
             lm->inv_pscale = (float)(1.0 / pscale);
-            if (hipMalloc((void**)&lm->Pfrag, (size_t)NG * 3 * KS * 64 * 8 * sizeof(_Float16)) != hipSuccess) return MOSHII_ERR_HIP;
-            if (hipMalloc((void**)&lm->perm, order.size() * sizeof(int)) != hipSuccess) return MOSHII_ERR_HIP;
+            if (hipMalloc((void**)&lm->Pfrag, (size_t)NG * 3 * KS * 64 * 8 * sizeof(_Float16)) != hipSuccess) return bad("Pfrag");
+            if (hipMalloc((void**)&lm->perm, order.size() * sizeof(int)) != hipSuccess) return bad("perm");
             // one allocation for the per-group tables (16-byte aligned parts): rounds | joint lists | exchange columns | rest positions | weights
             auto al16 = [](size_t n) { return (n + 15) & ~(size_t)15; };
             lm->tab_gnr = 0;
@@ -1609,9 +1616,9 @@ extern "C" int moshii_lbs32_prepare(moshii_model_t m) {
             lm->tab_gw = lm->tab_vshs + (unsigned)((size_t)NG * 16 * 4 * sizeof(float));
             lm->tab_vsc = lm->tab_gw + (unsigned)al16(gw.size() * sizeof(float));     // per call: rest + still correctives (k_lbs_still)
             const size_t tab_bytes = lm->tab_vsc + (size_t)NG * 16 * 4 * sizeof(float);
-            if (hipMalloc((void**)&lm->tables, tab_bytes) != hipSuccess) return MOSHII_ERR_HIP;
+            if (hipMalloc((void**)&lm->tables, tab_bytes) != hipSuccess) return bad("tables");
             hipMemset(lm->tables, 0, tab_bytes);
-            if (hipMalloc((void**)&lm->dbgbuf, 1024 * sizeof(long long)) != hipSuccess) return MOSHII_ERR_HIP;
+            if (hipMalloc((void**)&lm->dbgbuf, 1024 * sizeof(long long)) != hipSuccess) return bad("dbgbuf");
             hipMemset(lm->dbgbuf, 0, 1024 * sizeof(long long));
             hipMemcpy(lm->perm, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice);
             hipMemcpy(lm->tables + lm->tab_gx, gx.data(), gx.size() * sizeof(int), hipMemcpyHostToDevice);
@@ -1624,26 +1631,25 @@ extern "C" int moshii_lbs32_prepare(moshii_model_t m) {
     }
     // ---- the free shape block (declared, changed or cleared since the last prepare: moshii_model_set_free_shape clears l32_valid)
     {
-        if (hipDeviceSynchronize() != hipSuccess) return MOSHII_ERR_HIP;
+        if (hipDeviceSynchronize() != hipSuccess) return bad("(hipDeviceSynchronize)");
         free_ptr(lm->PfragX); free_ptr(lm->JSf); free_ptr(lm->Sft);
         lm->PfragX = nullptr; lm->JSf = nullptr; lm->Sft = nullptr; lm->nshape = 0; lm->KSX = 0; lm->sxscale = 1.0f;
         int NB = 0, start = 0, E = 0;
         const double* JS = nullptr;
         const double* sd = moshii_internal_shape_block(m, &NB, &start, &E, &JS);
         if (E > 0) {
-            if (hipMalloc((void**)&lm->JSf, (size_t)K * E * 4 * sizeof(float)) != hipSuccess) return MOSHII_ERR_HIP;
-            if (hipMalloc((void**)&lm->Sft, (size_t)E * 3 * Vp * sizeof(float)) != hipSuccess) return MOSHII_ERR_HIP;
+            if (hipMalloc((void**)&lm->JSf, (size_t)K * E * 4 * sizeof(float)) != hipSuccess) return bad("JSf");
+            if (hipMalloc((void**)&lm->Sft, (size_t)E * 3 * Vp * sizeof(float)) != hipSuccess) return bad("Sft");
             hipLaunchKernelGGL(k_cvt_js, dim3((K * E + 255) / 256), dim3(256), 0, 0, K * E, JS, lm->JSf);
             hipLaunchKernelGGL(k_cvt_shapedirs, dim3(1024), dim3(256), 0, 0, V, Vp, NB, start, E, sd, lm->Sft);
             lm->nshape = E;
             // (k_lbs_prep<true> keeps a frame's feature row in LDS: bodies whose pose and shape k-steps pass its size take the plain kernel)
             if (lm->mfma_ok && lm->KS + (3 * E + 31) / 32 <= LBS_PREP_KSMAX) {
-                double* d_part = nullptr;
-                if (hipMalloc((void**)&d_part, 256 * sizeof(double)) != hipSuccess) return MOSHII_ERR_HIP;
+                double* d_part = tmp.alloc<double>(256);
+                if (!d_part) return bad("the reduction buffer");
                 hipLaunchKernelGGL(k_absmax_block, dim3(256), dim3(256), 0, 0, (size_t)V * 3, NB, start, E, sd, d_part);
                 double part[256];
-                if (hipMemcpy(part, d_part, sizeof(part), hipMemcpyDeviceToHost) != hipSuccess) return MOSHII_ERR_HIP;
-                hipFree(d_part);
+                if (hipMemcpy(part, d_part, sizeof(part), hipMemcpyDeviceToHost) != hipSuccess) return bad("the reduction buffer (copy)");
                 double dmax = 0.0;
                 for (double p : part) dmax = std::max(dmax, p);
                 // Operand scales.  The accumulators carry pscale x metres; the block's directions can be far larger than the pose
@@ -1655,7 +1661,7 @@ extern "C" int moshii_lbs32_prepare(moshii_model_t m) {
                 lm->sxscale = (float)sx;
                 lm->KSX = (3 * E + 31) / 32;
                 const int NG = lm->NVT * 4, KST = lm->KSX + lm->KS;
-                if (hipMalloc((void**)&lm->PfragX, (size_t)NG * 3 * KST * 64 * 8 * sizeof(_Float16)) != hipSuccess) return MOSHII_ERR_HIP;
+                if (hipMalloc((void**)&lm->PfragX, (size_t)NG * 3 * KST * 64 * 8 * sizeof(_Float16)) != hipSuccess) return bad("PfragX");
                 hipLaunchKernelGGL(k_pack_pfrag_shape, dim3(4096), dim3(256), 0, 0, NB, start, E, lm->KSX, lm->KS, NG, (double)lm->pscale / sx, lm->perm, sd, lm->Pfrag, lm->PfragX);
             }
         }
@@ -1665,7 +1671,7 @@ extern "C" int moshii_lbs32_prepare(moshii_model_t m) {
     lm->jtab_valid = 0;
     if (lm->mfma_ok)   // rest positions in group order, x pscale (the accumulators start there)
         hipLaunchKernelGGL(k_pack_vsh, dim3((lm->NVT * LX_TV + 255) / 256), dim3(256), 0, 0, lm->NVT * LX_TV, lm->pscale, lm->perm, moshii_internal_vsh(m), reinterpret_cast<float*>(lm->tables + lm->tab_vshs));
-    if (hipDeviceSynchronize() != hipSuccess) return MOSHII_ERR_HIP;
+    if (hipDeviceSynchronize() != hipSuccess) return bad("(hipDeviceSynchronize)");
     moshii_internal_l32_set_valid(m, 1);
     return MOSHII_OK;
 }

@@ -1,6 +1,8 @@
 // libmoshii C ABI (include/moshii.h): handles, setup kernels, host-side staging and launch logic.
 #include "../../include/moshii.h"
 #include "moshii_dev.h"
+#include "dev_mem.h"
+#include "export_plan.h"
 #include "solve_plan.h"
 #include "stagei_views.h"
 
@@ -10,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -47,44 +50,24 @@ int fail(int code, const std::string& msg) { g_err = msg; return code; }
             return fail(MOSHII_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));            \
     } while (0)
 
-template <class T>
-int dev_upload(const T* host, size_t n, T** out) {
-    *out = nullptr;
-    if (n == 0) return MOSHII_OK;
-    HIP_TRY(hipMalloc((void**)out, n * sizeof(T)));
-    HIP_TRY(hipMemcpy(*out, host, n * sizeof(T), hipMemcpyHostToDevice));
-    return MOSHII_OK;
+// a failed device allocation or copy of `what` (an arena or a staging helper)
+template <class Mem>
+int fail_mem(const Mem& mem, const std::string& what) {
+    return fail(MOSHII_ERR_HIP, what + ": device allocation or copy failed: " + hipGetErrorString(mem.err()));
 }
 
-struct Scratch {   // growable device buffer reused across calls (small control data)
-    char* ptr = nullptr;
-    size_t cap = 0;
-    hipStream_t last_stream = nullptr;
-    bool used = false;
-    int reserve(size_t bytes) {
-        if (used) { hipStreamSynchronize(last_stream); used = false; }
-        if (bytes <= cap) return MOSHII_OK;
-        if (ptr) hipFree(ptr);
-        ptr = nullptr; cap = 0;
-        size_t want = std::max<size_t>(bytes, 1 << 16);
-        if (hipMalloc((void**)&ptr, want) != hipSuccess) return fail(MOSHII_ERR_HIP, "scratch hipMalloc failed");
-        cap = want;
-        return MOSHII_OK;
-    }
-    int reserve(size_t bytes, hipStream_t stream) {   // ... and the buffer is in use on `stream` until the next reserve
-        const int rc = reserve(bytes);
-        if (rc == MOSHII_OK) { used = true; last_stream = stream; }
-        return rc;
-    }
-    ~Scratch() { if (ptr) hipFree(ptr); }
-};
-
 }  // namespace
+
+extern "C" int moshii_internal_fail(int code, const char* msg) { return fail(code, msg); }   // (dev_mem.h, lbs_forward.hip)
+extern "C" void moshii_lbs32_free(void* l32);                                                // lbs_forward.hip
 
 struct moshii_model_s {
     int V = 0, K = 0, NB = 0, P = 0, NP = 0, body_dof = 0, hand_dof = 0, nhand_full = 0, maxdepth = 0;
     std::vector<int> parents, depth;
     std::vector<double> weights_host;   // [V][K] (attachment packing)
+    DevArena mem;                       // what moshii_model_create makes; the d_* below are views for dev() and the kernels
+    DevArena shape_mem;                 // d_JS, replaced as a whole by moshii_model_set_free_shape
+    DevArena face_mem;                  // d_vn_rows, d_vn_pairs, d_sd_tris, replaced as a whole by moshii_model_set_faces
     double *d_vt = nullptr, *d_shapedirs = nullptr, *d_posedirs = nullptr, *d_weights = nullptr, *d_Jreg = nullptr;
     double *d_vsh = nullptr, *d_J = nullptr, *d_hands_mean = nullptr, *d_comps = nullptr;
     double* d_JS = nullptr;             // [K][nshape][3] (moshii_model_set_free_shape)
@@ -95,8 +78,9 @@ struct moshii_model_s {
     int *d_parents = nullptr, *d_depth = nullptr, *d_comp_lo = nullptr, *d_comp_hi = nullptr, *d_col_lo = nullptr, *d_col_hi = nullptr;
     unsigned long long* d_anc = nullptr;
     bool betas_set = false;
-    Lbs32Model l32 = {};
+    Lbs32Model l32 = {};                // the f32 export's copy of the model (lbs_forward.hip builds, grows and frees it)
     bool l32_valid = false;
+    ~moshii_model_s() { moshii_lbs32_free(&l32); }
     Scratch scratch;
     // moshii_model_set_faces: vertex -> incident-corner table (CSR; lbs_forward.hip, "vertex normals"); null = no faces
     unsigned *d_vn_rows = nullptr, *d_vn_pairs = nullptr;
@@ -120,6 +104,7 @@ struct moshii_model_s {
 
 struct moshii_prior_s {
     int G = 0, npose = 0;
+    DevArena mem;
     double *d_means = nullptr, *d_chols = nullptr, *d_halfprec = nullptr, *d_neglogw = nullptr, *d_cnorm = nullptr;
     PriorDev dev() const {
         PriorDev p; p.G = G; p.npose = npose; p.means = as_gp(d_means); p.chols = as_gp(d_chols); p.halfprec = as_gp(d_halfprec);
@@ -131,6 +116,7 @@ struct moshii_prior_s {
 struct moshii_attach_s {
     moshii_model_t model = nullptr;
     int M = 0, Nv = 0, Nvp = 0, NW = 0;
+    DevArena mem;
     double *d_vsh = nullptr, *d_Pt = nullptr, *d_Pj = nullptr, *d_ww = nullptr, *d_coef = nullptr, *d_Ssh = nullptr;
     int nshape = 0;                     // free shape block gathered at creation (0: none)
     int* d_wj = nullptr;
@@ -414,7 +400,7 @@ int moshii_model_create(const moshii_model_desc* d, moshii_model_t* out) {
     const int nhf = P - d->body_dof;
     if ((d->hand_dof > 0) != (nhf > 0)) return fail(MOSHII_ERR_ARG, "hand_dof / body_dof mismatch");
     if (d->hand_dof > 0 && (!d->hands_mean || !d->selected_components)) return fail(MOSHII_ERR_ARG, "hand PCA arrays missing");
-    auto* m = new moshii_model_s();
+    std::unique_ptr<moshii_model_s> m(new moshii_model_s());   // (every failure below frees the handle and what it holds)
     m->V = d->V; m->K = d->K; m->NB = d->NB; m->P = P; m->body_dof = d->body_dof; m->hand_dof = d->hand_dof;
     m->nhand_full = nhf; m->NP = d->body_dof + d->hand_dof;
     m->parents.assign(d->parents, d->parents + d->K);
@@ -425,7 +411,7 @@ int moshii_model_create(const moshii_model_desc* d, moshii_model_t* out) {
         while (a >= 0) {
             anc[a] |= (1ull << j);
             const int p = m->parents[a];
-            if (p >= a) { delete m; return fail(MOSHII_ERR_ARG, "parents must precede children"); }
+            if (p >= a) return fail(MOSHII_ERR_ARG, "parents must precede children");
             a = p;
             if (a >= 0) ++dep;
         }
@@ -434,21 +420,21 @@ int moshii_model_create(const moshii_model_desc* d, moshii_model_t* out) {
     }
     m->weights_host.assign(d->weights, d->weights + (size_t)d->V * d->K);
     const size_t V = d->V, K = d->K, nfeat = 9 * (K - 1);
-    int rc;
-    if ((rc = dev_upload(d->v_template, V * 3, &m->d_vt))) return rc;
-    if ((rc = dev_upload(d->shapedirs, V * 3 * d->NB, &m->d_shapedirs))) return rc;
-    if ((rc = dev_upload(d->posedirs, V * 3 * nfeat, &m->d_posedirs))) return rc;
-    if ((rc = dev_upload(d->weights, V * K, &m->d_weights))) return rc;
-    if ((rc = dev_upload(d->J_regressor, K * V, &m->d_Jreg))) return rc;
-    if ((rc = dev_upload(m->parents.data(), K, &m->d_parents))) return rc;
+    DevArena& mem = m->mem;
+    m->d_vt = mem.upload(d->v_template, V * 3);
+    m->d_shapedirs = mem.upload(d->shapedirs, V * 3 * d->NB);
+    m->d_posedirs = mem.upload(d->posedirs, V * 3 * nfeat);
+    m->d_weights = mem.upload(d->weights, V * K);
+    m->d_Jreg = mem.upload(d->J_regressor, K * V);
+    m->d_parents = mem.upload(m->parents.data(), K);
     {   // behind the depths: the joints sorted by depth ([K]) and where each depth starts ([maxdepth + 2]) -- the level-by-level walks of the kernels
         std::vector<int> dl(m->depth);
         for (int l = 0; l <= m->maxdepth; ++l) for (size_t j = 0; j < K; ++j) if (m->depth[j] == l) dl.push_back((int)j);
         int c = 0;
         for (int l = 0; l <= m->maxdepth + 1; ++l) { dl.push_back(c); for (size_t j = 0; j < K; ++j) c += (m->depth[j] == l) ? 1 : 0; }
-        if ((rc = dev_upload(dl.data(), dl.size(), &m->d_depth))) return rc;
+        m->d_depth = mem.upload(dl.data(), dl.size());
     }
-    if ((rc = dev_upload(anc.data(), K, &m->d_anc))) return rc;
+    m->d_anc = mem.upload(anc.data(), K);
     if (d->hand_dof > 0) {
         std::vector<int> lo(d->hand_dof), hi(d->hand_dof);
         for (int i = 0; i < d->hand_dof; ++i) {
@@ -458,10 +444,10 @@ int moshii_model_create(const moshii_model_desc* d, moshii_model_t* out) {
             if (l > h) { l = 0; h = 0; }
             lo[i] = l; hi[i] = h;
         }
-        if ((rc = dev_upload(d->hands_mean, (size_t)nhf, &m->d_hands_mean))) return rc;
-        if ((rc = dev_upload(d->selected_components, (size_t)d->hand_dof * nhf, &m->d_comps))) return rc;
-        if ((rc = dev_upload(lo.data(), lo.size(), &m->d_comp_lo))) return rc;
-        if ((rc = dev_upload(hi.data(), hi.size(), &m->d_comp_hi))) return rc;
+        m->d_hands_mean = mem.upload(d->hands_mean, (size_t)nhf);
+        m->d_comps = mem.upload(d->selected_components, (size_t)d->hand_dof * nhf);
+        m->d_comp_lo = mem.upload(lo.data(), lo.size());
+        m->d_comp_hi = mem.upload(hi.data(), hi.size());
         std::vector<int> clo(nhf), chi(nhf);
         for (int c = 0; c < nhf; ++c) {
             int l = d->hand_dof, h = 0;
@@ -470,32 +456,21 @@ int moshii_model_create(const moshii_model_desc* d, moshii_model_t* out) {
             if (l > h) { l = 0; h = 0; }
             clo[c] = l; chi[c] = h;
         }
-        if ((rc = dev_upload(clo.data(), clo.size(), &m->d_col_lo))) return rc;
-        if ((rc = dev_upload(chi.data(), chi.size(), &m->d_col_hi))) return rc;
+        m->d_col_lo = mem.upload(clo.data(), clo.size());
+        m->d_col_hi = mem.upload(chi.data(), chi.size());
     }
-    HIP_TRY(hipMalloc((void**)&m->d_vsh, V * 3 * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&m->d_J, K * 3 * sizeof(double)));
-    *out = m;
+    m->d_vsh = mem.alloc<double>(V * 3);
+    m->d_J = mem.alloc<double>(K * 3);
+    if (!mem.ok()) return fail_mem(mem, "moshii_model_create");
     std::vector<double> zero(std::max(1, d->NB), 0.0);
-    return moshii_model_set_betas(m, zero.data(), d->NB);
-}
-
-extern "C" void moshii_lbs32_free(void* l32);   // lbs_forward.hip
-static void free_l32(moshii_model_s* m) {
-    moshii_lbs32_free(&m->l32);
-    m->l32_valid = false;
+    const int rc = moshii_model_set_betas(m.get(), zero.data(), d->NB);
+    if (rc == MOSHII_OK) *out = m.release();
+    return rc;
 }
 
 int moshii_model_destroy(moshii_model_t m) {
     if (!m) return MOSHII_OK;
     hipDeviceSynchronize();
-    void* ptrs[] = {m->d_vt, m->d_shapedirs, m->d_posedirs, m->d_weights, m->d_Jreg, m->d_vsh, m->d_J, m->d_hands_mean,
-                    m->d_comps, m->d_parents, m->d_depth, m->d_comp_lo, m->d_comp_hi, m->d_col_lo, m->d_col_hi, m->d_anc, m->d_JS};
-    for (void* p : ptrs) if (p) hipFree(p);
-    if (m->d_vn_rows) hipFree(m->d_vn_rows);
-    if (m->d_vn_pairs) hipFree(m->d_vn_pairs);
-    if (m->d_sd_tris) hipFree(m->d_sd_tris);
-    free_l32(m);
     delete m;
     return MOSHII_OK;
 }
@@ -503,15 +478,14 @@ int moshii_model_destroy(moshii_model_t m) {
 int moshii_model_set_betas(moshii_model_t m, const double* betas, int32_t nb) {
     if (!m || (!betas && nb > 0)) return fail(MOSHII_ERR_ARG, "null argument");
     nb = std::min<int32_t>(nb, m->NB);
-    double* d_b = nullptr;
-    int rc = dev_upload(betas, (size_t)std::max(nb, 0), &d_b);
-    if (rc) return rc;
+    DevArena tmp;
+    const double* d_b = tmp.upload(betas, (size_t)std::max(nb, 0));
+    if (!tmp.ok()) return fail_mem(tmp, "moshii_model_set_betas");
     const int tot = m->V * 3;
     hipLaunchKernelGGL(k_vshaped, dim3((tot + 255) / 256), dim3(256), 0, 0, m->V, m->NB, nb, m->d_vt, m->d_shapedirs, d_b, m->d_vsh);
     hipLaunchKernelGGL(k_joints, dim3(m->K), dim3(256), 0, 0, m->V, m->d_Jreg, m->d_vsh, m->d_J);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    if (d_b) hipFree(d_b);
     m->betas_set = true;
     m->l32_valid = false;
     return MOSHII_OK;
@@ -521,14 +495,19 @@ int moshii_model_set_free_shape(moshii_model_t m, int32_t start, int32_t count) 
     if (!m || start < 0 || count < 0 || start + count > m->NB) return fail(MOSHII_ERR_ARG, "free shape block outside shapedirs");
     if (count > 125) return fail(MOSHII_ERR_UNSUPPORTED, "at most 125 free shape coefficients");
     HIP_TRY(hipDeviceSynchronize());
-    if (m->d_JS) { hipFree(m->d_JS); m->d_JS = nullptr; }
-    m->shape_start = start; m->nshape = count;
+    // the old block goes first; the new one is published only when it is whole: a failure leaves the handle without a block
+    m->shape_mem.clear();
+    m->d_JS = nullptr; m->shape_start = 0; m->nshape = 0;
     m->l32_valid = false;   // the f32 export's fragments and scratch sizes depend on the block
-    if (count == 0) return MOSHII_OK;
-    HIP_TRY(hipMalloc((void**)&m->d_JS, (size_t)m->K * count * 3 * sizeof(double)));
-    hipLaunchKernelGGL(k_shape_joints, dim3(m->K * count), dim3(256), 0, 0, m->V, m->NB, start, count, m->d_Jreg, m->d_shapedirs, m->d_JS);
+    if (count == 0) { m->shape_start = start; return MOSHII_OK; }
+    DevArena fresh;
+    double* d_JS = fresh.alloc<double>((size_t)m->K * count * 3);
+    if (!fresh.ok()) return fail_mem(fresh, "moshii_model_set_free_shape");
+    hipLaunchKernelGGL(k_shape_joints, dim3(m->K * count), dim3(256), 0, 0, m->V, m->NB, start, count, m->d_Jreg, m->d_shapedirs, d_JS);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
+    m->shape_mem = std::move(fresh);
+    m->d_JS = d_JS; m->shape_start = start; m->nshape = count;
     return MOSHII_OK;
 }
 
@@ -552,89 +531,260 @@ static void launch_lbs_f64(moshii_model_t m, int F, const double* d_pose, const 
     }
 }
 
-// shape: per-frame coefficients of the free block [F][nshape], or null (the frozen body)
-static int lbs_forward_f64_impl(moshii_model_t m, int32_t F, const double* pose, const double* trans, const double* shape, double* verts,
-                                uint32_t flags, void* stream_) {
-    if (!m || !pose || !trans || !verts || F < 0) return fail(MOSHII_ERR_ARG, "bad argument");
-    if (shape && m->nshape == 0) return fail(MOSHII_ERR_ARG, "shape coefficients without a block: call moshii_model_set_free_shape first");
-    if (F == 0) return MOSHII_OK;
-    hipStream_t stream = (hipStream_t)stream_;
-    const bool dev = (flags & MOSHII_BUFFERS_DEVICE) != 0;
-    const double *d_pose = pose, *d_trans = trans, *d_shape = shape;
-    double* d_out = verts;
-    double *t_pose = nullptr, *t_trans = nullptr, *t_shape = nullptr, *t_out = nullptr;
-    if (!dev) {
-        int rc;
-        if ((rc = dev_upload(pose, (size_t)F * m->NP, &t_pose))) return rc;
-        if ((rc = dev_upload(trans, (size_t)F * 3, &t_trans))) return rc;
-        if (shape && (rc = dev_upload(shape, (size_t)F * m->nshape, &t_shape))) return rc;
-        HIP_TRY(hipMalloc((void**)&t_out, (size_t)F * m->V * 3 * sizeof(double)));
-        d_pose = t_pose; d_trans = t_trans; d_out = t_out;
-        if (shape) d_shape = t_shape;
-    }
-    launch_lbs_f64(m, F, d_pose, d_trans, d_shape, d_out, stream);
-    HIP_TRY(hipGetLastError());
-    if (!dev) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipMemcpy(verts, t_out, (size_t)F * m->V * 3 * sizeof(double), hipMemcpyDeviceToHost));
-        hipFree(t_pose); hipFree(t_trans); hipFree(t_out);
-        if (t_shape) hipFree(t_shape);
-    }
-    return MOSHII_OK;
-}
-
-int moshii_lbs_forward_f64(moshii_model_t m, int32_t F, const double* pose, const double* trans, double* verts,
-                           uint32_t flags, void* stream) {
-    return lbs_forward_f64_impl(m, F, pose, trans, nullptr, verts, flags, stream);
-}
-
-int moshii_lbs_forward_shape_f64(moshii_model_t m, int32_t F, const double* pose, const double* trans, const double* shape,
-                                 double* verts, uint32_t flags, void* stream) {
-    return lbs_forward_f64_impl(m, F, pose, trans, shape, verts, flags, stream);
-}
-
 // implemented in lbs_forward.hip
 int moshii_lbs32_prepare(moshii_model_t m);
 
-static int lbs_forward_f32_impl(moshii_model_t m, int32_t F, const float* pose, const float* trans, const float* shape, float* verts,
-                                uint32_t flags, void* stream_) {
-    if (!m || !pose || !trans || !verts || F < 0) return fail(MOSHII_ERR_ARG, "bad argument");
+}  // extern "C"
+
+// ---- what the export entries share ----
+namespace {
+int need_shape_block(moshii_model_t m, const void* shape) {
     if (shape && m->nshape == 0) return fail(MOSHII_ERR_ARG, "shape coefficients without a block: call moshii_model_set_free_shape first");
+    return MOSHII_OK;
+}
+int need_faces(moshii_model_t m, const char* name) {
+    if (!m->d_vn_rows) return fail(MOSHII_ERR_ARG, std::string(name) + ": the model has no faces: call moshii_model_set_faces first");
+    return MOSHII_OK;
+}
+template <class T> int need_l32(moshii_model_t m) {   // the f32 export works on its own copy of the model
+    return (sizeof(T) == 4 && !m->l32_valid) ? moshii_lbs32_prepare(m) : MOSHII_OK;
+}
+
+// one export of nf frames, pointers on the device: the kernels of moshii_lbs_forward[_shape]_*
+hipError_t export_batch(moshii_model_t m, int nf, const float* pose, const float* trans, const float* shape, float* out, hipStream_t stream) {
+    ModelDev md = m->dev();
+    const hipError_t e = moshii_launch_lbs_f32(stream, &md, nf, pose, trans, shape, out, &m->l32);
+    if (e != hipSuccess) { moshii_lbs32_free(&m->l32); m->l32_valid = false; }   // (no half-grown copy is kept: the next call builds it again)
+    return e;
+}
+hipError_t export_batch(moshii_model_t m, int nf, const double* pose, const double* trans, const double* shape, double* out, hipStream_t stream) {
+    launch_lbs_f64(m, nf, pose, trans, shape, out, stream);
+    return hipGetLastError();
+}
+
+// MOSHII_VM_BATCH (tests: batch boundaries with few frames), 0 = unset
+int batch_override() {
+    const char* es = getenv("MOSHII_VM_BATCH");
+    return es ? std::max(1, atoi(es)) : 0;
+}
+}  // namespace
+
+// shape: per-frame coefficients of the free block [F][nshape], or null (the frozen body)
+template <class T>
+static int lbs_forward_impl(moshii_model_t m, int32_t F, const T* pose, const T* trans, const T* shape, T* verts, uint32_t flags, void* stream_) {
+    if (!m || !pose || !trans || !verts || F < 0) return fail(MOSHII_ERR_ARG, "bad argument");
+    if (int rc = need_shape_block(m, shape)) return rc;
     if (F == 0) return MOSHII_OK;
     hipStream_t stream = (hipStream_t)stream_;
-    if (!m->l32_valid) { int rc = moshii_lbs32_prepare(m); if (rc) return rc; }
-    const bool dev = (flags & MOSHII_BUFFERS_DEVICE) != 0;
-    const float *d_pose = pose, *d_trans = trans, *d_shape = shape;
-    float* d_out = verts;
-    float *t_pose = nullptr, *t_trans = nullptr, *t_shape = nullptr, *t_out = nullptr;
-    if (!dev) {
-        int rc;
-        if ((rc = dev_upload(pose, (size_t)F * m->NP, &t_pose))) return rc;
-        if ((rc = dev_upload(trans, (size_t)F * 3, &t_trans))) return rc;
-        if (shape && (rc = dev_upload(shape, (size_t)F * m->nshape, &t_shape))) return rc;
-        HIP_TRY(hipMalloc((void**)&t_out, (size_t)F * m->V * 3 * sizeof(float)));
-        d_pose = t_pose; d_trans = t_trans; d_out = t_out;
-        if (shape) d_shape = t_shape;
-    }
-    ModelDev md = m->dev();
-    HIP_TRY(moshii_launch_lbs_f32(stream, &md, F, d_pose, d_trans, d_shape, d_out, &m->l32));
-    if (!dev) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipMemcpy(verts, t_out, (size_t)F * m->V * 3 * sizeof(float), hipMemcpyDeviceToHost));
-        hipFree(t_pose); hipFree(t_trans); hipFree(t_out);
-        if (t_shape) hipFree(t_shape);
-    }
+    Staging st(flags, stream);
+    const T* d_pose = st.in(pose, (size_t)F * m->NP);
+    const T* d_trans = st.in(trans, (size_t)F * 3);
+    const T* d_shape = st.in(shape, (size_t)F * m->nshape);
+    T* d_out = st.out(verts, (size_t)F * m->V * 3);
+    if (!st.ok()) return fail_mem(st, "moshii_lbs_forward");
+    if (int rc = need_l32<T>(m)) return rc;   // (behind the staging: a call that cannot stage its buffers builds nothing)
+    HIP_TRY(export_batch(m, F, d_pose, d_trans, d_shape, d_out, stream));
+    HIP_TRY(st.finish());
     return MOSHII_OK;
 }
 
-int moshii_lbs_forward_f32(moshii_model_t m, int32_t F, const float* pose, const float* trans, float* verts,
-                           uint32_t flags, void* stream) {
-    return lbs_forward_f32_impl(m, F, pose, trans, nullptr, verts, flags, stream);
+template <class T>
+static int vertex_normals_impl(moshii_model_t m, int32_t F, const T* verts, T* normals, uint32_t flags, void* stream_, const char* name) {
+    if (!m || !verts || !normals || F < 0) return fail(MOSHII_ERR_ARG, std::string(name) + ": bad argument");
+    if (int rc = need_faces(m, name)) return rc;
+    if (F == 0) return MOSHII_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t n = (size_t)F * m->V * 3;
+    Staging st(flags, stream);
+    const T* d_in = st.in(verts, n);
+    T* d_out = st.out(normals, n);
+    if (!st.ok()) return fail_mem(st, name);
+    const char* which = "";
+    int lds = 0, threads = 0;
+    HIP_TRY(moshii_launch_vertex_normals(stream, m->V, F, sizeof(T) == 8, d_in, d_out, m->d_vn_rows, m->d_vn_pairs, m->vn_w16, &which, &lds, &threads));
+    note_launch(which, lds, threads);
+    HIP_TRY(st.finish());
+    return MOSHII_OK;
 }
 
+// The meshes exist only in the handle's scratch, a batch of frames at a time: export (the kernels of moshii_lbs_forward[_shape]_*, so
+// the same vertices bit for bit as that call gives for the batch's frames), then the normals of the M marker vertices alone.
+template <class T>
+static int virtual_markers_impl(moshii_model_t m, int32_t F, const T* pose, const T* trans, const T* shape, int32_t M, const int32_t* vids,
+                                const T* dist, T* markers, T* mnormals, uint32_t flags, void* stream_, const char* name) {
+    if (!m || !pose || !trans || !vids || !dist || !markers || F < 0 || M < 1) return fail(MOSHII_ERR_ARG, std::string(name) + ": bad argument");
+    if (int rc = need_shape_block(m, shape)) return rc;
+    if (int rc = need_faces(m, name)) return rc;
+    for (int i = 0; i < M; ++i) if (vids[i] < 0 || vids[i] >= m->V) return fail(MOSHII_ERR_ARG, std::string(name) + ": marker vertex id outside [0, V)");
+    if (F == 0) return MOSHII_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = need_l32<T>(m)) return rc;
+    const export_plan::Batch bp = export_plan::plan_batch((size_t)m->V * 3 * sizeof(T), F, M, sizeof(T) == 8, batch_override());
+    if (int rc = m->vmscratch.reserve(bp.vm_bytes)) return rc;   // (waits for the call before this one)
+    T* d_mesh = reinterpret_cast<T*>(m->vmscratch.ptr);
+    int* d_vids = reinterpret_cast<int*>(m->vmscratch.ptr + bp.off_vids);
+    double* d_dist = reinterpret_cast<double*>(m->vmscratch.ptr + bp.off_dist);
+    std::vector<double> dist64(dist, dist + M);
+    HIP_TRY(hipMemcpy(d_vids, vids, (size_t)M * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_dist, dist64.data(), (size_t)M * sizeof(double), hipMemcpyHostToDevice));
+    const size_t nout = (size_t)F * M * 3;
+    Staging st(flags, stream);
+    const T* d_pose = st.in(pose, (size_t)F * m->NP);
+    const T* d_trans = st.in(trans, (size_t)F * 3);
+    const T* d_shape = st.in(shape, (size_t)F * m->nshape);
+    T* d_out = st.out(markers, nout);
+    T* d_nrm = st.out(mnormals, nout);
+    if (!st.ok()) return fail_mem(st, name);
+    m->vmscratch.used = true; m->vmscratch.last_stream = stream;
+    for (long long f0 = 0; f0 < F; f0 += bp.batch) {
+        const int nf = (int)std::min<long long>(bp.batch, F - f0);
+        HIP_TRY(export_batch(m, nf, d_pose + (size_t)f0 * m->NP, d_trans + (size_t)f0 * 3,
+                             d_shape ? d_shape + (size_t)f0 * m->nshape : (const T*)nullptr, d_mesh, stream));
+        HIP_TRY(moshii_launch_marker_normals(stream, m->V, nf, M, sizeof(T) == 8, d_mesh, d_vids, d_dist, d_out + (size_t)f0 * M * 3,
+                                             d_nrm ? d_nrm + (size_t)f0 * M * 3 : (T*)nullptr, m->d_vn_rows, m->d_vn_pairs, m->vn_w16));
+    }
+    HIP_TRY(st.finish());
+    return MOSHII_OK;
+}
+
+// ---- signed point-to-mesh distance (version 105) ----
+namespace {
+const char* sd_check(moshii_model_t m, int32_t F, int32_t N, const void* dist) {
+    if (!m) return "null model";
+    if (F < 0 || N < 0) return "negative F or N";
+    if (!dist) return "dist is null";
+    return nullptr;
+}
+}  // namespace
+
+// verts / points / outputs on the device; `face` may be null (the winners then go to d_win)
+template <class T>
+static int surface_distance_launch(moshii_model_t m, int F, const T* d_verts, int N, const T* d_points, T* d_dist, int* d_face, int* d_part,
+                                   T* d_near, int* d_win, hipStream_t stream) {
+    const char* which = "";
+    int lds = 0, threads = 0;
+    HIP_TRY(moshii_launch_surface_distance(stream, m->V, m->n_faces, F, N, sizeof(T) == 8, d_verts, d_points, m->d_sd_tris, m->vn_w16, m->d_vn_rows,
+                                           m->d_vn_pairs, d_dist, d_face ? d_face : d_win, d_part, d_near, &which, &lds, &threads));
+    note_launch(which, lds, threads);
+    return MOSHII_OK;
+}
+
+template <class T>
+static int surface_distance_impl(moshii_model_t m, int32_t F, const T* verts, int32_t N, const T* points, T* dist, int32_t* face, int32_t* part,
+                                 T* nearest, uint32_t flags, void* stream_, const char* name) {
+    if (const char* bad = sd_check(m, F, N, dist)) return fail(MOSHII_ERR_ARG, std::string(name) + ": " + bad);
+    if (int rc = need_faces(m, name)) return rc;
+    if (F == 0 || N == 0) return MOSHII_OK;
+    if (!verts || !points) return fail(MOSHII_ERR_ARG, std::string(name) + ": verts or points is null");
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t nv = (size_t)F * m->V * 3, np = (size_t)F * N;
+    Staging st(flags, stream);
+    int* d_win = nullptr;   // the search's winners when the caller takes no `face`: the handle's scratch, or a temporary of this call
+    if (!face && st.device()) {
+        if (int rc = m->sdscratch.reserve(np * sizeof(int), stream)) return rc;   // (waits for the call before this one)
+        d_win = reinterpret_cast<int*>(m->sdscratch.ptr);
+    }
+    const T* d_verts = st.in(verts, nv);
+    const T* d_points = st.in(points, np * 3);
+    T* d_dist = st.out(dist, np);
+    int* d_face = st.out(face, np);
+    if (!face && !st.device()) d_win = st.mem().alloc<int>(np);
+    int* d_part = st.out(part, np);
+    T* d_near = st.out(nearest, np * 3);
+    if (!st.ok()) return fail_mem(st, name);
+    if (int rc = surface_distance_launch(m, F, d_verts, N, d_points, d_dist, d_face, d_part, d_near, d_win, stream)) return rc;
+    HIP_TRY(st.finish());
+    return MOSHII_OK;
+}
+
+// The meshes exist only in the handle's scratch, a batch of frames at a time, sized and exported as moshii_virtual_markers_* does;
+// each batch's points meet their own frames' meshes there and only the F x N results leave.
+template <class T>
+static int marker_surface_distance_impl(moshii_model_t m, int32_t F, const T* pose, const T* trans, const T* shape, int32_t N, const T* points,
+                                        T* dist, int32_t* face, int32_t* part, T* nearest, uint32_t flags, void* stream_, const char* name) {
+    if (const char* bad = sd_check(m, F, N, dist)) return fail(MOSHII_ERR_ARG, std::string(name) + ": " + bad);
+    if (int rc = need_shape_block(m, shape)) return rc;
+    if (int rc = need_faces(m, name)) return rc;
+    if (F == 0 || N == 0) return MOSHII_OK;
+    if (!pose || !trans || !points) return fail(MOSHII_ERR_ARG, std::string(name) + ": pose, trans or points is null");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = need_l32<T>(m)) return rc;
+    const export_plan::Batch bp = export_plan::plan_batch((size_t)m->V * 3 * sizeof(T), F, N, sizeof(T) == 8, batch_override());
+    if (int rc = m->vmscratch.reserve(face ? bp.sd_bytes_face : bp.sd_bytes)) return rc;   // (waits for the call before this one)
+    T* d_mesh = reinterpret_cast<T*>(m->vmscratch.ptr);
+    int* d_win = face ? (int*)nullptr : reinterpret_cast<int*>(m->vmscratch.ptr + bp.off_win);
+    const size_t np = (size_t)F * N;
+    Staging st(flags, stream);
+    const T* d_pose = st.in(pose, (size_t)F * m->NP);
+    const T* d_trans = st.in(trans, (size_t)F * 3);
+    const T* d_shape = st.in(shape, (size_t)F * m->nshape);
+    const T* d_points = st.in(points, np * 3);
+    T* d_dist = st.out(dist, np);
+    int* d_face = st.out(face, np);
+    int* d_part = st.out(part, np);
+    T* d_near = st.out(nearest, np * 3);
+    if (!st.ok()) return fail_mem(st, name);
+    m->vmscratch.used = true; m->vmscratch.last_stream = stream;
+    for (long long f0 = 0; f0 < F; f0 += bp.batch) {
+        const int nf = (int)std::min<long long>(bp.batch, F - f0);
+        const size_t at = (size_t)f0 * N;
+        HIP_TRY(export_batch(m, nf, d_pose + (size_t)f0 * m->NP, d_trans + (size_t)f0 * 3,
+                             d_shape ? d_shape + (size_t)f0 * m->nshape : (const T*)nullptr, d_mesh, stream));
+        if (int rc = surface_distance_launch(m, nf, (const T*)d_mesh, N, d_points + at * 3, d_dist + at, d_face ? d_face + at : (int*)nullptr,
+                                             d_part ? d_part + at : (int*)nullptr, d_near ? d_near + at * 3 : (T*)nullptr, d_win, stream)) return rc;
+    }
+    HIP_TRY(st.finish());
+    return MOSHII_OK;
+}
+
+// ---- posed joints and world joint rotations (version 106) ----
+// Nothing of the handle is written: no scratch, no f32 copy, no faces -- the kernel reads the model arrays and the caller's buffers, so
+// the call may run beside an export of the same handle on another stream.
+template <class T>
+static int joints_impl(moshii_model_t m, int32_t F, const T* pose, const T* trans, const T* shape, T* joints, T* rot, uint32_t flags,
+                       void* stream_, const char* name) {
+    if (!m) return fail(MOSHII_ERR_ARG, std::string(name) + ": null model");
+    if (F < 0) return fail(MOSHII_ERR_ARG, std::string(name) + ": negative F");
+    if (!joints) return fail(MOSHII_ERR_ARG, std::string(name) + ": joints is null");
+    if (!m->betas_set) return fail(MOSHII_ERR_ARG, std::string(name) + ": moshii_model_set_betas has not been called");
+    if (int rc = need_shape_block(m, shape)) return rc;
+    if (F == 0) return MOSHII_OK;
+    if (!pose || !trans) return fail(MOSHII_ERR_ARG, std::string(name) + ": pose or trans is null");
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t nj = (size_t)F * m->K * 3;
+    Staging st(flags, stream);
+    const T* d_pose = st.in(pose, (size_t)F * m->NP);
+    const T* d_trans = st.in(trans, (size_t)F * 3);
+    const T* d_shape = st.in(shape, (size_t)F * m->nshape);
+    T* d_joints = st.out(joints, nj);
+    T* d_rot = st.out(rot, nj * 3);
+    if (!st.ok()) return fail_mem(st, name);
+    const ModelDev md = m->dev();
+    const char* which = "";
+    int threads = 0;
+    HIP_TRY(moshii_launch_joints(stream, &md, F, sizeof(T) == 8, d_pose, d_trans, d_shape, d_joints, d_rot, &which, &threads));
+    note_launch(which, 0, threads);
+    HIP_TRY(st.finish());
+    return MOSHII_OK;
+}
+
+extern "C" {
+
+int moshii_lbs_forward_f64(moshii_model_t m, int32_t F, const double* pose, const double* trans, double* verts,
+                           uint32_t flags, void* stream) {
+    return lbs_forward_impl<double>(m, F, pose, trans, nullptr, verts, flags, stream);
+}
+int moshii_lbs_forward_shape_f64(moshii_model_t m, int32_t F, const double* pose, const double* trans, const double* shape,
+                                 double* verts, uint32_t flags, void* stream) {
+    return lbs_forward_impl(m, F, pose, trans, shape, verts, flags, stream);
+}
+int moshii_lbs_forward_f32(moshii_model_t m, int32_t F, const float* pose, const float* trans, float* verts,
+                           uint32_t flags, void* stream) {
+    return lbs_forward_impl<float>(m, F, pose, trans, nullptr, verts, flags, stream);
+}
 int moshii_lbs_forward_shape_f32(moshii_model_t m, int32_t F, const float* pose, const float* trans, const float* shape,
                                  float* verts, uint32_t flags, void* stream) {
-    return lbs_forward_f32_impl(m, F, pose, trans, shape, verts, flags, stream);
+    return lbs_forward_impl(m, F, pose, trans, shape, verts, flags, stream);
 }
 
 // ---- faces, vertex normals, virtual markers (version 104) ----
@@ -645,9 +795,8 @@ int moshii_model_set_faces(moshii_model_t m, int32_t n_faces, const int32_t* fac
     for (size_t i = 0; i < (size_t)n_faces * 3; ++i)
         if (faces[i] < 0 || faces[i] >= V) return fail(MOSHII_ERR_ARG, "moshii_model_set_faces: vertex id outside [0, V)");
     HIP_TRY(hipDeviceSynchronize());
-    if (m->d_vn_rows) { hipFree(m->d_vn_rows); m->d_vn_rows = nullptr; }
-    if (m->d_vn_pairs) { hipFree(m->d_vn_pairs); m->d_vn_pairs = nullptr; }
-    if (m->d_sd_tris) { hipFree(m->d_sd_tris); m->d_sd_tris = nullptr; }
+    m->face_mem.clear();
+    m->d_vn_rows = nullptr; m->d_vn_pairs = nullptr; m->d_sd_tris = nullptr;
     m->n_faces = 0;
     if (n_faces == 0) return MOSHII_OK;
     // vertex -> incident corners: for vertex v of face (a, b, c) the other two in cyclic order, (p - v) x (q - v) = the face's scaled
@@ -677,58 +826,17 @@ int moshii_model_set_faces(moshii_model_t m, int32_t n_faces, const int32_t* fac
         else for (int c = 0; c < 3; ++c) tris[3 * f + c] = (unsigned)t[c];
     }
     // every part uploaded before any is published: a failure leaves the handle without a table, never with half of one
-    unsigned *d_rows = nullptr, *d_pairs = nullptr, *d_tris = nullptr;
-    int rc;
-    if ((rc = dev_upload(rows.data(), rows.size(), &d_rows))) return rc;
-    if ((rc = dev_upload(pairs.data(), pairs.size(), &d_pairs))) { hipFree(d_rows); return rc; }
-    if ((rc = dev_upload(tris.data(), tris.size(), &d_tris))) { hipFree(d_rows); hipFree(d_pairs); return rc; }
+    DevArena fresh;
+    unsigned* d_rows = fresh.upload(rows.data(), rows.size());
+    unsigned* d_pairs = fresh.upload(pairs.data(), pairs.size());
+    unsigned* d_tris = fresh.upload(tris.data(), tris.size());
+    if (!fresh.ok()) return fail_mem(fresh, "moshii_model_set_faces");
+    m->face_mem = std::move(fresh);
     m->d_vn_rows = d_rows; m->d_vn_pairs = d_pairs; m->d_sd_tris = d_tris;
     m->n_faces = n_faces;
     m->vn_w16 = w16 ? 1 : 0;
     return MOSHII_OK;
 }
-
-}  // extern "C"
-
-namespace {
-struct DevTemps {   // device temporaries of a host-buffer call: freed on every way out
-    std::vector<void*> ptrs;
-    template <class T> T* keep(T* p) { ptrs.push_back((void*)p); return p; }
-    ~DevTemps() { for (void* p : ptrs) if (p) hipFree(p); }
-};
-}  // namespace
-
-template <class T>
-static int vertex_normals_impl(moshii_model_t m, int32_t F, const T* verts, T* normals, uint32_t flags, void* stream_, const char* name) {
-    if (!m || !verts || !normals || F < 0) return fail(MOSHII_ERR_ARG, std::string(name) + ": bad argument");
-    if (!m->d_vn_rows) return fail(MOSHII_ERR_ARG, std::string(name) + ": the model has no faces: call moshii_model_set_faces first");
-    if (F == 0) return MOSHII_OK;
-    hipStream_t stream = (hipStream_t)stream_;
-    const bool dev = (flags & MOSHII_BUFFERS_DEVICE) != 0;
-    const size_t n = (size_t)F * m->V * 3;
-    const T* d_in = verts;
-    T *d_out = normals, *t_in = nullptr, *t_out = nullptr;
-    DevTemps temps;
-    if (!dev) {
-        int rc = dev_upload(verts, n, &t_in);
-        temps.keep(t_in);
-        if (rc) return rc;
-        HIP_TRY(hipMalloc((void**)&t_out, n * sizeof(T)));
-        temps.keep(t_out);
-        d_in = t_in; d_out = t_out;
-    }
-    const char* which = "";
-    int lds = 0, threads = 0;
-    HIP_TRY(moshii_launch_vertex_normals(stream, m->V, F, sizeof(T) == 8, d_in, d_out, m->d_vn_rows, m->d_vn_pairs, m->vn_w16, &which, &lds, &threads));
-    note_launch(which, lds, threads);
-    if (!dev) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipMemcpy(normals, t_out, n * sizeof(T), hipMemcpyDeviceToHost));
-    }
-    return MOSHII_OK;
-}
-
-extern "C" {
 
 int moshii_vertex_normals_f32(moshii_model_t m, int32_t F, const float* verts, float* normals, uint32_t flags, void* stream) {
     return vertex_normals_impl(m, F, verts, normals, flags, stream, "moshii_vertex_normals_f32");
@@ -736,82 +844,6 @@ int moshii_vertex_normals_f32(moshii_model_t m, int32_t F, const float* verts, f
 int moshii_vertex_normals_f64(moshii_model_t m, int32_t F, const double* verts, double* normals, uint32_t flags, void* stream) {
     return vertex_normals_impl(m, F, verts, normals, flags, stream, "moshii_vertex_normals_f64");
 }
-
-}  // extern "C"
-
-static hipError_t export_batch(moshii_model_t m, int nf, const float* pose, const float* trans, const float* shape, float* out, hipStream_t stream) {
-    ModelDev md = m->dev();
-    return moshii_launch_lbs_f32(stream, &md, nf, pose, trans, shape, out, &m->l32);
-}
-static hipError_t export_batch(moshii_model_t m, int nf, const double* pose, const double* trans, const double* shape, double* out, hipStream_t stream) {
-    launch_lbs_f64(m, nf, pose, trans, shape, out, stream);
-    return hipGetLastError();
-}
-
-// The meshes exist only in the handle's scratch, a batch of frames at a time: export (the kernels of moshii_lbs_forward[_shape]_*, so
-// the same vertices bit for bit as that call gives for the batch's frames), then the normals of the M marker vertices alone.
-template <class T>
-static int virtual_markers_impl(moshii_model_t m, int32_t F, const T* pose, const T* trans, const T* shape, int32_t M, const int32_t* vids,
-                                const T* dist, T* markers, T* mnormals, uint32_t flags, void* stream_, const char* name) {
-    if (!m || !pose || !trans || !vids || !dist || !markers || F < 0 || M < 1) return fail(MOSHII_ERR_ARG, std::string(name) + ": bad argument");
-    if (shape && m->nshape == 0) return fail(MOSHII_ERR_ARG, "shape coefficients without a block: call moshii_model_set_free_shape first");
-    if (!m->d_vn_rows) return fail(MOSHII_ERR_ARG, std::string(name) + ": the model has no faces: call moshii_model_set_faces first");
-    for (int i = 0; i < M; ++i) if (vids[i] < 0 || vids[i] >= m->V) return fail(MOSHII_ERR_ARG, std::string(name) + ": marker vertex id outside [0, V)");
-    if (F == 0) return MOSHII_OK;
-    hipStream_t stream = (hipStream_t)stream_;
-    if (sizeof(T) == 4 && !m->l32_valid) { int rc = moshii_lbs32_prepare(m); if (rc) return rc; }
-    const bool dev = (flags & MOSHII_BUFFERS_DEVICE) != 0;
-    const size_t frame_bytes = (size_t)m->V * 3 * sizeof(T);
-    // frames per batch: 256 MB of meshes (SMPL-H f32: 2 816 frames), whole 128-frame tiles of the f32 export where it reaches one
-    long long batch = std::max<long long>(1, (long long)((size_t)256 << 20) / (long long)frame_bytes);
-    if (batch >= 128) batch = batch / 128 * 128;
-    if (const char* es = getenv("MOSHII_VM_BATCH")) batch = std::max(1, atoi(es));   // (tests: batch boundaries with few frames)
-    batch = std::min<long long>(std::min<long long>(batch, F), 0x7fffffffLL / M);
-    if (sizeof(T) == 8) batch = std::min<long long>(batch, 65535);   // (the f64 export puts the frames on grid.y)
-    const size_t off_vids = ((size_t)batch * frame_bytes + 15) & ~(size_t)15, off_dist = (off_vids + (size_t)M * sizeof(int) + 15) & ~(size_t)15;
-    int rc = m->vmscratch.reserve(off_dist + (size_t)M * sizeof(double));   // (waits for the call before this one)
-    if (rc) return rc;
-    T* d_mesh = reinterpret_cast<T*>(m->vmscratch.ptr);
-    int* d_vids = reinterpret_cast<int*>(m->vmscratch.ptr + off_vids);
-    double* d_dist = reinterpret_cast<double*>(m->vmscratch.ptr + off_dist);
-    std::vector<double> dist64(dist, dist + M);
-    HIP_TRY(hipMemcpy(d_vids, vids, (size_t)M * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_dist, dist64.data(), (size_t)M * sizeof(double), hipMemcpyHostToDevice));
-    const T *d_pose = pose, *d_trans = trans, *d_shape = shape;
-    T *d_out = markers, *d_nrm = mnormals;
-    T *t_pose = nullptr, *t_trans = nullptr, *t_shape = nullptr, *t_out = nullptr, *t_nrm = nullptr;
-    const size_t nout = (size_t)F * M * 3;
-    DevTemps temps;
-    if (!dev) {
-        rc = dev_upload(pose, (size_t)F * m->NP, &t_pose); temps.keep(t_pose);
-        if (rc) return rc;
-        rc = dev_upload(trans, (size_t)F * 3, &t_trans); temps.keep(t_trans);
-        if (rc) return rc;
-        if (shape) { rc = dev_upload(shape, (size_t)F * m->nshape, &t_shape); temps.keep(t_shape); if (rc) return rc; }
-        HIP_TRY(hipMalloc((void**)&t_out, nout * sizeof(T)));
-        temps.keep(t_out);
-        if (mnormals) { HIP_TRY(hipMalloc((void**)&t_nrm, nout * sizeof(T))); temps.keep(t_nrm); }
-        d_pose = t_pose; d_trans = t_trans; d_out = t_out; d_nrm = t_nrm;
-        if (shape) d_shape = t_shape;
-    }
-    m->vmscratch.used = true; m->vmscratch.last_stream = stream;
-    for (long long f0 = 0; f0 < F; f0 += batch) {
-        const int nf = (int)std::min<long long>(batch, F - f0);
-        HIP_TRY(export_batch(m, nf, d_pose + (size_t)f0 * m->NP, d_trans + (size_t)f0 * 3,
-                             d_shape ? d_shape + (size_t)f0 * m->nshape : (const T*)nullptr, d_mesh, stream));
-        HIP_TRY(moshii_launch_marker_normals(stream, m->V, nf, M, sizeof(T) == 8, d_mesh, d_vids, d_dist, d_out + (size_t)f0 * M * 3,
-                                             d_nrm ? d_nrm + (size_t)f0 * M * 3 : (T*)nullptr, m->d_vn_rows, m->d_vn_pairs, m->vn_w16));
-    }
-    if (!dev) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipMemcpy(markers, t_out, nout * sizeof(T), hipMemcpyDeviceToHost));
-        if (mnormals) HIP_TRY(hipMemcpy(mnormals, t_nrm, nout * sizeof(T), hipMemcpyDeviceToHost));
-    }
-    return MOSHII_OK;
-}
-
-extern "C" {
-
 int moshii_virtual_markers_f32(moshii_model_t m, int32_t F, const float* pose, const float* trans, const float* shape, int32_t M,
                                const int32_t* vids, const float* dist, float* markers, float* marker_normals, uint32_t flags, void* stream) {
     return virtual_markers_impl(m, F, pose, trans, shape, M, vids, dist, markers, marker_normals, flags, stream, "moshii_virtual_markers_f32");
@@ -820,139 +852,6 @@ int moshii_virtual_markers_f64(moshii_model_t m, int32_t F, const double* pose, 
                                const int32_t* vids, const double* dist, double* markers, double* marker_normals, uint32_t flags, void* stream) {
     return virtual_markers_impl(m, F, pose, trans, shape, M, vids, dist, markers, marker_normals, flags, stream, "moshii_virtual_markers_f64");
 }
-
-}  // extern "C"
-
-// ---- signed point-to-mesh distance (version 105) ----
-namespace {
-const char* sd_check(moshii_model_t m, int32_t F, int32_t N, const void* dist) {
-    if (!m) return "null model";
-    if (F < 0 || N < 0) return "negative F or N";
-    if (!dist) return "dist is null";
-    return nullptr;
-}
-}  // namespace
-
-// verts / points / outputs on the device; `face` may be null (the winners then go to the handle's scratch)
-template <class T>
-static int surface_distance_launch(moshii_model_t m, int F, const T* d_verts, int N, const T* d_points, T* d_dist, int* d_face, int* d_part,
-                                   T* d_near, int* d_win, hipStream_t stream) {
-    const char* which = "";
-    int lds = 0, threads = 0;
-    HIP_TRY(moshii_launch_surface_distance(stream, m->V, m->n_faces, F, N, sizeof(T) == 8, d_verts, d_points, m->d_sd_tris, m->vn_w16, m->d_vn_rows,
-                                           m->d_vn_pairs, d_dist, d_face ? d_face : d_win, d_part, d_near, &which, &lds, &threads));
-    note_launch(which, lds, threads);
-    return MOSHII_OK;
-}
-
-template <class T>
-static int surface_distance_impl(moshii_model_t m, int32_t F, const T* verts, int32_t N, const T* points, T* dist, int32_t* face, int32_t* part,
-                                 T* nearest, uint32_t flags, void* stream_, const char* name) {
-    if (const char* bad = sd_check(m, F, N, dist)) return fail(MOSHII_ERR_ARG, std::string(name) + ": " + bad);
-    if (!m->d_sd_tris) return fail(MOSHII_ERR_ARG, std::string(name) + ": the model has no faces: call moshii_model_set_faces first");
-    if (F == 0 || N == 0) return MOSHII_OK;
-    if (!verts || !points) return fail(MOSHII_ERR_ARG, std::string(name) + ": verts or points is null");
-    hipStream_t stream = (hipStream_t)stream_;
-    const bool dev = (flags & MOSHII_BUFFERS_DEVICE) != 0;
-    const size_t nv = (size_t)F * m->V * 3, np = (size_t)F * N;
-    if (dev) {
-        int* d_win = nullptr;
-        if (!face) {
-            int rc = m->sdscratch.reserve(np * sizeof(int), stream);   // (waits for the call before this one)
-            if (rc) return rc;
-            d_win = reinterpret_cast<int*>(m->sdscratch.ptr);
-        }
-        return surface_distance_launch(m, F, verts, N, points, dist, face, part, nearest, d_win, stream);
-    }
-    DevTemps temps;
-    T *t_verts = nullptr, *t_points = nullptr, *t_dist = nullptr, *t_near = nullptr;
-    int *t_face = nullptr, *t_part = nullptr;
-    int rc = dev_upload(verts, nv, &t_verts); temps.keep(t_verts);
-    if (rc) return rc;
-    rc = dev_upload(points, np * 3, &t_points); temps.keep(t_points);
-    if (rc) return rc;
-    HIP_TRY(hipMalloc((void**)&t_dist, np * sizeof(T))); temps.keep(t_dist);
-    HIP_TRY(hipMalloc((void**)&t_face, np * sizeof(int))); temps.keep(t_face);
-    if (part) { HIP_TRY(hipMalloc((void**)&t_part, np * sizeof(int))); temps.keep(t_part); }
-    if (nearest) { HIP_TRY(hipMalloc((void**)&t_near, np * 3 * sizeof(T))); temps.keep(t_near); }
-    rc = surface_distance_launch(m, F, t_verts, N, t_points, t_dist, t_face, t_part, t_near, (int*)nullptr, stream);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(stream));
-    HIP_TRY(hipMemcpy(dist, t_dist, np * sizeof(T), hipMemcpyDeviceToHost));
-    if (face) HIP_TRY(hipMemcpy(face, t_face, np * sizeof(int), hipMemcpyDeviceToHost));
-    if (part) HIP_TRY(hipMemcpy(part, t_part, np * sizeof(int), hipMemcpyDeviceToHost));
-    if (nearest) HIP_TRY(hipMemcpy(nearest, t_near, np * 3 * sizeof(T), hipMemcpyDeviceToHost));
-    return MOSHII_OK;
-}
-
-// The meshes exist only in the handle's scratch, a batch of frames at a time, sized and exported as moshii_virtual_markers_* does;
-// each batch's points meet their own frames' meshes there and only the F x N results leave.
-template <class T>
-static int marker_surface_distance_impl(moshii_model_t m, int32_t F, const T* pose, const T* trans, const T* shape, int32_t N, const T* points,
-                                        T* dist, int32_t* face, int32_t* part, T* nearest, uint32_t flags, void* stream_, const char* name) {
-    if (const char* bad = sd_check(m, F, N, dist)) return fail(MOSHII_ERR_ARG, std::string(name) + ": " + bad);
-    if (shape && m->nshape == 0) return fail(MOSHII_ERR_ARG, "shape coefficients without a block: call moshii_model_set_free_shape first");
-    if (!m->d_sd_tris) return fail(MOSHII_ERR_ARG, std::string(name) + ": the model has no faces: call moshii_model_set_faces first");
-    if (F == 0 || N == 0) return MOSHII_OK;
-    if (!pose || !trans || !points) return fail(MOSHII_ERR_ARG, std::string(name) + ": pose, trans or points is null");
-    hipStream_t stream = (hipStream_t)stream_;
-    if (sizeof(T) == 4 && !m->l32_valid) { int rc = moshii_lbs32_prepare(m); if (rc) return rc; }
-    const bool dev = (flags & MOSHII_BUFFERS_DEVICE) != 0;
-    const size_t frame_bytes = (size_t)m->V * 3 * sizeof(T);
-    long long batch = std::max<long long>(1, (long long)((size_t)256 << 20) / (long long)frame_bytes);
-    if (batch >= 128) batch = batch / 128 * 128;
-    if (const char* es = getenv("MOSHII_VM_BATCH")) batch = std::max(1, atoi(es));   // (tests: batch boundaries with few frames)
-    batch = std::min<long long>(std::min<long long>(batch, F), 0x7fffffffLL / N);
-    if (sizeof(T) == 8) batch = std::min<long long>(batch, 65535);   // (the f64 export puts the frames on grid.y)
-    const size_t off_win = ((size_t)batch * frame_bytes + 15) & ~(size_t)15;
-    int rc = m->vmscratch.reserve(off_win + (face ? 0 : (size_t)batch * N * sizeof(int)));   // (waits for the call before this one)
-    if (rc) return rc;
-    T* d_mesh = reinterpret_cast<T*>(m->vmscratch.ptr);
-    int* d_win = face ? (int*)nullptr : reinterpret_cast<int*>(m->vmscratch.ptr + off_win);
-    const T *d_pose = pose, *d_trans = trans, *d_shape = shape, *d_points = points;
-    T *d_dist = dist, *d_near = nearest;
-    int *d_face = face, *d_part = part;
-    T *t_pose = nullptr, *t_trans = nullptr, *t_shape = nullptr, *t_points = nullptr, *t_dist = nullptr, *t_near = nullptr;
-    int *t_face = nullptr, *t_part = nullptr;
-    const size_t np = (size_t)F * N;
-    DevTemps temps;
-    if (!dev) {
-        rc = dev_upload(pose, (size_t)F * m->NP, &t_pose); temps.keep(t_pose);
-        if (rc) return rc;
-        rc = dev_upload(trans, (size_t)F * 3, &t_trans); temps.keep(t_trans);
-        if (rc) return rc;
-        if (shape) { rc = dev_upload(shape, (size_t)F * m->nshape, &t_shape); temps.keep(t_shape); if (rc) return rc; }
-        rc = dev_upload(points, np * 3, &t_points); temps.keep(t_points);
-        if (rc) return rc;
-        HIP_TRY(hipMalloc((void**)&t_dist, np * sizeof(T))); temps.keep(t_dist);
-        if (face) { HIP_TRY(hipMalloc((void**)&t_face, np * sizeof(int))); temps.keep(t_face); }
-        if (part) { HIP_TRY(hipMalloc((void**)&t_part, np * sizeof(int))); temps.keep(t_part); }
-        if (nearest) { HIP_TRY(hipMalloc((void**)&t_near, np * 3 * sizeof(T))); temps.keep(t_near); }
-        d_pose = t_pose; d_trans = t_trans; d_points = t_points; d_dist = t_dist; d_face = t_face; d_part = t_part; d_near = t_near;
-        if (shape) d_shape = t_shape;
-    }
-    m->vmscratch.used = true; m->vmscratch.last_stream = stream;
-    for (long long f0 = 0; f0 < F; f0 += batch) {
-        const int nf = (int)std::min<long long>(batch, F - f0);
-        const size_t at = (size_t)f0 * N;
-        HIP_TRY(export_batch(m, nf, d_pose + (size_t)f0 * m->NP, d_trans + (size_t)f0 * 3,
-                             d_shape ? d_shape + (size_t)f0 * m->nshape : (const T*)nullptr, d_mesh, stream));
-        rc = surface_distance_launch(m, nf, (const T*)d_mesh, N, d_points + at * 3, d_dist + at, d_face ? d_face + at : (int*)nullptr,
-                                     d_part ? d_part + at : (int*)nullptr, d_near ? d_near + at * 3 : (T*)nullptr, d_win, stream);
-        if (rc) return rc;
-    }
-    if (!dev) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipMemcpy(dist, t_dist, np * sizeof(T), hipMemcpyDeviceToHost));
-        if (face) HIP_TRY(hipMemcpy(face, t_face, np * sizeof(int), hipMemcpyDeviceToHost));
-        if (part) HIP_TRY(hipMemcpy(part, t_part, np * sizeof(int), hipMemcpyDeviceToHost));
-        if (nearest) HIP_TRY(hipMemcpy(nearest, t_near, np * 3 * sizeof(T), hipMemcpyDeviceToHost));
-    }
-    return MOSHII_OK;
-}
-
-extern "C" {
-
 int moshii_surface_distance_f32(moshii_model_t m, int32_t F, const float* verts, int32_t N, const float* points, float* dist, int32_t* face,
                                 int32_t* part, float* nearest, uint32_t flags, void* stream) {
     return surface_distance_impl(m, F, verts, N, points, dist, face, part, nearest, flags, stream, "moshii_surface_distance_f32");
@@ -969,54 +868,6 @@ int moshii_marker_surface_distance_f64(moshii_model_t m, int32_t F, const double
                                        const double* points, double* dist, int32_t* face, int32_t* part, double* nearest, uint32_t flags, void* stream) {
     return marker_surface_distance_impl(m, F, pose, trans, shape, N, points, dist, face, part, nearest, flags, stream, "moshii_marker_surface_distance_f64");
 }
-
-}  // extern "C"
-
-// ---- posed joints and world joint rotations (version 106) ----
-// Nothing of the handle is written: no scratch, no f32 copy, no faces -- the kernel reads the model arrays and the caller's buffers, so
-// the call may run beside an export of the same handle on another stream.
-template <class T>
-static int joints_impl(moshii_model_t m, int32_t F, const T* pose, const T* trans, const T* shape, T* joints, T* rot, uint32_t flags,
-                       void* stream_, const char* name) {
-    if (!m) return fail(MOSHII_ERR_ARG, std::string(name) + ": null model");
-    if (F < 0) return fail(MOSHII_ERR_ARG, std::string(name) + ": negative F");
-    if (!joints) return fail(MOSHII_ERR_ARG, std::string(name) + ": joints is null");
-    if (!m->betas_set) return fail(MOSHII_ERR_ARG, std::string(name) + ": moshii_model_set_betas has not been called");
-    if (shape && m->nshape == 0) return fail(MOSHII_ERR_ARG, "shape coefficients without a block: call moshii_model_set_free_shape first");
-    if (F == 0) return MOSHII_OK;
-    if (!pose || !trans) return fail(MOSHII_ERR_ARG, std::string(name) + ": pose or trans is null");
-    hipStream_t stream = (hipStream_t)stream_;
-    const bool dev = (flags & MOSHII_BUFFERS_DEVICE) != 0;
-    const size_t nj = (size_t)F * m->K * 3;
-    const T *d_pose = pose, *d_trans = trans, *d_shape = shape;
-    T *d_joints = joints, *d_rot = rot;
-    DevTemps temps;
-    if (!dev) {
-        T *t_pose = nullptr, *t_trans = nullptr, *t_shape = nullptr, *t_joints = nullptr, *t_rot = nullptr;
-        int rc = dev_upload(pose, (size_t)F * m->NP, &t_pose); temps.keep(t_pose);
-        if (rc) return rc;
-        rc = dev_upload(trans, (size_t)F * 3, &t_trans); temps.keep(t_trans);
-        if (rc) return rc;
-        if (shape) { rc = dev_upload(shape, (size_t)F * m->nshape, &t_shape); temps.keep(t_shape); if (rc) return rc; }
-        HIP_TRY(hipMalloc((void**)&t_joints, nj * sizeof(T))); temps.keep(t_joints);
-        if (rot) { HIP_TRY(hipMalloc((void**)&t_rot, nj * 3 * sizeof(T))); temps.keep(t_rot); }
-        d_pose = t_pose; d_trans = t_trans; d_shape = t_shape; d_joints = t_joints; d_rot = t_rot;
-    }
-    const ModelDev md = m->dev();
-    const char* which = "";
-    int threads = 0;
-    HIP_TRY(moshii_launch_joints(stream, &md, F, sizeof(T) == 8, d_pose, d_trans, d_shape, d_joints, d_rot, &which, &threads));
-    note_launch(which, 0, threads);
-    if (!dev) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipMemcpy(joints, d_joints, nj * sizeof(T), hipMemcpyDeviceToHost));
-        if (rot) HIP_TRY(hipMemcpy(rot, d_rot, nj * 3 * sizeof(T), hipMemcpyDeviceToHost));
-    }
-    return MOSHII_OK;
-}
-
-extern "C" {
-
 int moshii_joints_f32(moshii_model_t m, int32_t F, const float* pose, const float* trans, const float* shape, float* joints, float* rot,
                       uint32_t flags, void* stream) {
     return joints_impl(m, F, pose, trans, shape, joints, rot, flags, stream, "moshii_joints_f32");
@@ -1031,7 +882,7 @@ int moshii_prior_create(int32_t G, int32_t npose, const double* means, const dou
     if (!means || !chols || !weights || !out || G < 1 || npose < 1) return fail(MOSHII_ERR_ARG, "bad argument");
     if (npose > 127) return fail(MOSHII_ERR_UNSUPPORTED, "prior npose > 127 (the chain kernel takes a prior's columns two per lane)");
     if (moshii_device_count() < 1) return fail(MOSHII_ERR_NO_DEVICE, "no HIP device: libmoshii has no CPU path");
-    auto* p = new moshii_prior_s();
+    std::unique_ptr<moshii_prior_s> p(new moshii_prior_s());
     p->G = G; p->npose = npose;
     const size_t nn = (size_t)npose * npose;
     std::vector<double> half((size_t)G * nn), nlw(G), cn(G), lower((size_t)G * nn, 0.0);   // lower: the factors with explicit zeros above the
@@ -1058,25 +909,23 @@ int moshii_prior_create(int32_t G, int32_t npose, const double* means, const dou
         for (int j = 0; j < npose; ++j) n1 = std::max(n1, colsum[j]);
         cn[g] = std::min(std::sqrt(fro), std::sqrt(n1 * ninf)) * 0.70710678118654757 * (1.0 + 1e-12);
     }
-    int rc;
     // (means and factors carry 16 entries / rows of zero padding: the chain kernel reads whole 16-row groups unclamped)
     std::vector<double> means_p((size_t)G * npose + 16, 0.0);
     std::copy(means, means + (size_t)G * npose, means_p.begin());
     lower.resize((size_t)G * nn + (size_t)16 * npose, 0.0);
-    if ((rc = dev_upload(means_p.data(), means_p.size(), &p->d_means))) return rc;
-    if ((rc = dev_upload(lower.data(), lower.size(), &p->d_chols))) return rc;
-    if ((rc = dev_upload(half.data(), half.size(), &p->d_halfprec))) return rc;
-    if ((rc = dev_upload(nlw.data(), nlw.size(), &p->d_neglogw))) return rc;
-    if ((rc = dev_upload(cn.data(), cn.size(), &p->d_cnorm))) return rc;
-    *out = p;
+    p->d_means = p->mem.upload(means_p.data(), means_p.size());
+    p->d_chols = p->mem.upload(lower.data(), lower.size());
+    p->d_halfprec = p->mem.upload(half.data(), half.size());
+    p->d_neglogw = p->mem.upload(nlw.data(), nlw.size());
+    p->d_cnorm = p->mem.upload(cn.data(), cn.size());
+    if (!p->mem.ok()) return fail_mem(p->mem, "moshii_prior_create");
+    *out = p.release();
     return MOSHII_OK;
 }
 
 int moshii_prior_destroy(moshii_prior_t p) {
     if (!p) return MOSHII_OK;
     hipDeviceSynchronize();
-    void* ptrs[] = {p->d_means, p->d_chols, p->d_halfprec, p->d_neglogw, p->d_cnorm};
-    for (void* q : ptrs) if (q) hipFree(q);
     delete p;
     return MOSHII_OK;
 }
@@ -1084,13 +933,13 @@ int moshii_prior_destroy(moshii_prior_t p) {
 int moshii_attach_create(moshii_model_t m, int32_t M, const int32_t* closest, const double* coef, moshii_attach_t* out) {
     if (!m || !closest || !coef || !out || M < 1) return fail(MOSHII_ERR_ARG, "bad argument");
     if (M > 128) return fail(MOSHII_ERR_UNSUPPORTED, "at most 128 latent markers");
-    auto* a = new moshii_attach_s();
+    std::unique_ptr<moshii_attach_s> a(new moshii_attach_s());
     a->model = m; a->M = M; a->Nv = 3 * M; a->Nvp = (a->Nv + 7) & ~7;
     std::vector<int> vids(a->Nv);
     int NW = 1;
     for (int i = 0; i < a->Nv; ++i) {
         vids[i] = closest[i];
-        if (vids[i] < 0 || vids[i] >= m->V) { delete a; return fail(MOSHII_ERR_ARG, "vertex id out of range"); }
+        if (vids[i] < 0 || vids[i] >= m->V) return fail(MOSHII_ERR_ARG, "vertex id out of range");
         int c = 0;
         for (int j = 0; j < m->K; ++j) if (m->weights_host[(size_t)vids[i] * m->K + j] != 0.0) ++c;
         NW = std::max(NW, c);
@@ -1105,15 +954,16 @@ int moshii_attach_create(moshii_model_t m, int32_t M, const int32_t* closest, co
             if (w != 0.0) { wj[(size_t)i * NW + c] = j; ww[(size_t)i * NW + c] = w; ++c; }
         }
     }
-    int rc;
-    if ((rc = dev_upload(vids.data(), vids.size(), &a->d_vids))) return rc;
-    if ((rc = dev_upload(wj.data(), wj.size(), &a->d_wj))) return rc;
-    if ((rc = dev_upload(ww.data(), ww.size(), &a->d_ww))) return rc;
-    if ((rc = dev_upload(coef, (size_t)M * 3, &a->d_coef))) return rc;
-    HIP_TRY(hipMalloc((void**)&a->d_vsh, (size_t)a->Nv * 3 * sizeof(double)));
+    DevArena& mem = a->mem;
+    a->d_vids = mem.upload(vids.data(), vids.size());
+    a->d_wj = mem.upload(wj.data(), wj.size());
+    a->d_ww = mem.upload(ww.data(), ww.size());
+    a->d_coef = mem.upload(coef, (size_t)M * 3);
+    a->d_vsh = mem.alloc<double>((size_t)a->Nv * 3);
     const size_t npt = (size_t)(m->K - 1) * 27 * a->Nvp;
-    HIP_TRY(hipMalloc((void**)&a->d_Pt, std::max<size_t>(npt, 1) * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&a->d_Pj, std::max<size_t>((size_t)(m->K - 1) * 3 * 14 * M * 2, 1) * sizeof(double)));
+    a->d_Pt = mem.alloc<double>(npt);
+    a->d_Pj = mem.alloc<double>((size_t)(m->K - 1) * 3 * 14 * M * 2);
+    if (!mem.ok()) return fail_mem(mem, "moshii_attach_create");
     const int blocks = (int)std::min<size_t>(4096, std::max<size_t>((npt + 255) / 256, (size_t)(a->Nv * 3 + 255) / 256));
     hipLaunchKernelGGL(k_pack_attach, dim3(std::max(blocks, 1)), dim3(256), 0, 0, a->Nv, a->Nvp, m->K, a->d_vids, m->d_posedirs,
                        m->d_vsh, a->d_Pt, a->d_Pj, a->d_vsh);
@@ -1121,7 +971,8 @@ int moshii_attach_create(moshii_model_t m, int32_t M, const int32_t* closest, co
     if (m->nshape > 0) {   // rows of the free shape block (moshii_model_set_free_shape)
         a->nshape = m->nshape;
         const size_t ns = (size_t)m->nshape * 3 * a->Nvp;
-        HIP_TRY(hipMalloc((void**)&a->d_Ssh, ns * sizeof(double)));
+        a->d_Ssh = mem.alloc<double>(ns);
+        if (!mem.ok()) return fail_mem(mem, "moshii_attach_create");
         hipLaunchKernelGGL(k_pack_shape, dim3((unsigned)std::min<size_t>(4096, (ns + 255) / 256)), dim3(256), 0, 0, a->Nv, a->Nvp, m->NB,
                            m->shape_start, m->nshape, a->d_vids, m->d_shapedirs, a->d_Ssh);
         HIP_TRY(hipGetLastError());
@@ -1131,16 +982,15 @@ int moshii_attach_create(moshii_model_t m, int32_t M, const int32_t* closest, co
     av.M = M; av.Nv = a->Nv; av.Nvp = a->Nvp; av.NW = NW;
     av.vsh = as_gp(a->d_vsh); av.Pt = as_gp(a->d_Pt); av.Pj = as_gp(a->d_Pj); av.wj = as_gp(a->d_wj); av.ww = as_gp(a->d_ww);
     av.coef = as_gp(a->d_coef); av.Ssh = as_gp(a->d_Ssh);
-    if ((rc = dev_upload(&av, 1, &a->d_self))) return rc;
-    *out = a;
+    a->d_self = mem.upload(&av, 1);
+    if (!mem.ok()) return fail_mem(mem, "moshii_attach_create");
+    *out = a.release();
     return MOSHII_OK;
 }
 
 int moshii_attach_destroy(moshii_attach_t a) {
     if (!a) return MOSHII_OK;
     hipDeviceSynchronize();
-    void* ptrs[] = {a->d_vsh, a->d_Pt, a->d_Pj, a->d_ww, a->d_coef, a->d_wj, a->d_vids, a->d_self, a->d_Ssh};
-    for (void* q : ptrs) if (q) hipFree(q);
     delete a;
     return MOSHII_OK;
 }
@@ -1150,16 +1000,14 @@ int moshii_attach_markers(moshii_attach_t a, int32_t F, const double* pose, cons
     if (F == 0) return MOSHII_OK;
     moshii_model_t m = a->model;
     ChainLayout ly = make_layout(m, a->M, a->Nv, a->NW, 0, 0, 16, 1, 1);
-    double *d_pose = nullptr, *d_trans = nullptr, *d_out = nullptr;
-    int rc;
-    if ((rc = dev_upload(pose, (size_t)F * m->NP, &d_pose))) return rc;
-    if ((rc = dev_upload(trans, (size_t)F * 3, &d_trans))) return rc;
-    HIP_TRY(hipMalloc((void**)&d_out, (size_t)F * a->M * 3 * sizeof(double)));
+    Staging st(MOSHII_BUFFERS_HOST, nullptr);   // (host buffers, the null stream)
+    const double* d_pose = st.in(pose, (size_t)F * m->NP);
+    const double* d_trans = st.in(trans, (size_t)F * 3);
+    double* d_out = st.out(markers, (size_t)F * a->M * 3);
+    if (!st.ok()) return fail_mem(st, "moshii_attach_markers");
     ModelDev md = m->dev();
     HIP_TRY(moshii_launch_markers(F, (size_t)ly.total_doubles * sizeof(double), 0, a->d_self, &md, &ly, d_pose, d_trans, d_out));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(markers, d_out, (size_t)F * a->M * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    hipFree(d_pose); hipFree(d_trans); hipFree(d_out);
+    HIP_TRY(st.finish());
     return MOSHII_OK;
 }
 
@@ -1444,48 +1292,31 @@ struct FrameBufs {   // the per-frame arrays shared by moshii_chain_desc and mos
 };
 struct Staged {   // device copies of one chain's / sequence's per-frame host buffers: freed on every way out
     FrameBufs rows = {};
-    Staged() = default;
-    Staged(const Staged&) = delete;
-    Staged& operator=(const Staged&) = delete;
-    Staged(Staged&& o) noexcept : rows(o.rows) { o.rows = {}; }
-    Staged& operator=(Staged&& o) noexcept { std::swap(rows, o.rows); return *this; }
-    ~Staged() {
-        const void* ptrs[] = {rows.obs, rows.vis, rows.pose, rows.fullpose, rows.trans, rows.msim, rows.errs, rows.iters, rows.status, rows.shape};
-        for (const void* q : ptrs) if (q) hipFree(const_cast<void*>(q));
-    }
+    DevArena mem;   // owns what `rows` points to
 };
 struct CallBufs {
     std::vector<Staged> st;      // per chain / sequence; empty for MOSHII_BUFFERS_DEVICE callers
-    double* d_init = nullptr;    // moshii_sequence_solve: start states of the sequences that continue a chain
+    DevArena mem;                // moshii_sequence_solve: start states of the sequences that continue a chain
     explicit CallBufs(size_t n) : st(n) {}
-    CallBufs(const CallBufs&) = delete;
-    CallBufs& operator=(const CallBufs&) = delete;
-    ~CallBufs() { if (d_init) hipFree(d_init); }
 };
-
-template <class T>
-hipError_t dev_zeros(T** out, size_t n, hipStream_t stream) {
-    const hipError_t e = hipMalloc((void**)out, n * sizeof(T));
-    return e != hipSuccess ? e : hipMemsetAsync(*out, 0, n * sizeof(T), stream);
-}
 
 // device copies of the inputs of `h`, zeroed rows for its outputs (n_shape > 0: and that many shape coefficients)
 int stage_in(const FrameBufs& h, int NP, int P, size_t n_shape, hipStream_t stream, Staged* s) {
     const size_t Fz = std::max(h.F, 1), M = h.M;
     FrameBufs& d = s->rows;
     d.F = h.F; d.M = h.M;
-    int rc;
-    if ((rc = dev_upload(h.obs, (size_t)h.F * M * 3, const_cast<double**>(&d.obs)))) return rc;
-    if ((rc = dev_upload(h.vis, (size_t)h.F * M, const_cast<uint8_t**>(&d.vis)))) return rc;
-    HIP_TRY(dev_zeros(&d.pose, Fz * NP, stream));
-    HIP_TRY(dev_zeros(&d.fullpose, Fz * P, stream));
-    HIP_TRY(dev_zeros(&d.trans, Fz * 3, stream));
-    HIP_TRY(dev_zeros(&d.msim, Fz * M * 3, stream));
-    HIP_TRY(dev_zeros(&d.errs, Fz * MOSHII_NERR, stream));
-    HIP_TRY(dev_zeros(&d.iters, Fz * 2, stream));
-    HIP_TRY(dev_zeros(&d.status, Fz, stream));
-    if (n_shape > 0) HIP_TRY(dev_zeros(&d.shape, n_shape, stream));
-    return MOSHII_OK;
+    DevArena& mem = s->mem;
+    d.obs = mem.upload(h.obs, (size_t)h.F * M * 3);
+    d.vis = mem.upload(h.vis, (size_t)h.F * M);
+    d.pose = mem.zeros<double>(Fz * NP, stream);
+    d.fullpose = mem.zeros<double>(Fz * P, stream);
+    d.trans = mem.zeros<double>(Fz * 3, stream);
+    d.msim = mem.zeros<double>(Fz * M * 3, stream);
+    d.errs = mem.zeros<double>(Fz * MOSHII_NERR, stream);
+    d.iters = mem.zeros<int>(Fz * 2, stream);
+    d.status = mem.zeros<int>(Fz, stream);
+    if (n_shape > 0) d.shape = mem.zeros<double>(n_shape, stream);
+    return mem.ok() ? MOSHII_OK : fail_mem(mem, "staging a chain's frames");
 }
 
 // copies the results back (the stream has been synchronised); `s` frees the device copies when it goes
@@ -1636,6 +1467,7 @@ struct SeqSolve {
     bool fuse = false, trace = false;
     std::vector<LaunchCfg> coop_cfgs = std::vector<LaunchCfg>(MOSHII_COOP_MAXG + 1);   // per group size, prepared when first used (coop_g set)
     CallBufs bufs{dev ? (size_t)0 : (size_t)n_seq};   // the device buffers of this call: released on EVERY way out of it
+    const double* d_init = nullptr;                   // start states of the sequences that continue a chain (in bufs.mem)
     std::vector<FrameBufs> fbs, dbs;                  // the caller's rows; where the chains find them on the device
     size_t qbytes = 0;
     std::vector<double> hdev;    // the last verification's hand-off deviations / verdicts
@@ -1715,8 +1547,8 @@ struct SeqSolve {
                 h[2 * NP + 4] = 0.0;
                 if (E > 0 && sq.init_shape) memcpy(h + 2 * NP + 5, sq.init_shape, sizeof(double) * E);
             }
-            HIP_TRY(hipMalloc((void**)&bufs.d_init, hinit.size() * sizeof(double)));
-            HIP_TRY(hipMemcpy(bufs.d_init, hinit.data(), hinit.size() * sizeof(double), hipMemcpyHostToDevice));
+            d_init = bufs.mem.upload(hinit.data(), hinit.size());
+            if (!bufs.mem.ok()) return fail_mem(bufs.mem, "moshii_sequence_solve: start states");
         }
         fbs.resize(n_seq); dbs.resize(n_seq);
         for (int q = 0; q < n_seq; ++q) {
@@ -1760,8 +1592,8 @@ struct SeqSolve {
         if (repair) {
             cd.init_state = d_final + (size_t)ck.pred * S;
             cd.rejoin_tol = rejoin ? tol : 0.0;
-        } else if (ck.pred < 0 && bufs.d_init != nullptr && seqs[ck.seq].init_pose != nullptr) {
-            cd.init_state = bufs.d_init + (size_t)ck.seq * S;   // the sequence continues a chain instead of starting one
+        } else if (ck.pred < 0 && d_init != nullptr && seqs[ck.seq].init_pose != nullptr) {
+            cd.init_state = d_init + (size_t)ck.seq * S;   // the sequence continues a chain instead of starting one
         }
         return cd;
     }

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include "stagei_views.h"
 #include "stagei_plan.h"
+#include "dev_mem.h"
 #include "../../include/moshii.h"
 #include <math.h>
 #include <stdio.h>
@@ -1385,23 +1386,6 @@ KERNEL k_s1_back(const int* fcols, int fs, const int* scols, int ns, int nsp, co
 namespace sp = stagei_plan;
 using sp::Vec;
 
-struct DevPool {        // every device allocation of one solve; freed together
-    std::vector<void*> ptrs;
-    bool ok = true;
-    template <class T> T* get(size_t count) {
-        void* q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) { ok = false; return nullptr; }
-        ptrs.push_back(q);
-        return (T*)q;
-    }
-    template <class T> T* put(const T* src, size_t count, hipStream_t st) {
-        T* q = get<T>(count);
-        if (q && count) hipMemcpyAsync(q, src, count * sizeof(T), hipMemcpyHostToDevice, st);
-        return q;
-    }
-    ~DevPool() { for (void* q : ptrs) hipFree(q); }
-};
-
 // The blocked Cholesky factorisation of A (n x n, in place; dinv: the panels' inverse diagonal blocks; status[1]: a pivot was not positive)
 void s1_chol_factor(double* A, int n, double* dinv, int* status, hipStream_t st) {
     for (int j0 = 0; j0 < n; j0 += S1_PB) {
@@ -1448,17 +1432,17 @@ void s1_arrow_solve(const S1Arrow& a, double* out, bool clear_out, int scatter_s
 // allreduce_on_device the callback works on device memory (RCCL): device buffers are summed in place, host vectors are staged through
 // d_red; without it the callback works on host memory (gloo, or nccl behind a copy) and device buffers take the round trip through `hred`.
 struct RankSum {
-    const moshii_stagei_desc* ds; hipStream_t st; DevPool& pool;
+    const moshii_stagei_desc* ds; hipStream_t st; DevArena& pool;
     const bool on, dev;
     int rc = 0;                 // a callback (or a staging allocation) failed
     double* d_red = nullptr; long long cap = 0;
     Vec hred;
-    RankSum(const moshii_stagei_desc* ds_, hipStream_t st_, DevPool& pool_)
+    RankSum(const moshii_stagei_desc* ds_, hipStream_t st_, DevArena& pool_)
         : ds(ds_), st(st_), pool(pool_), on(ds_->sharded && ds_->allreduce_sum), dev(on && ds_->allreduce_on_device) {}
     void reduce(double* buf, long long count) {
         if (!on || count <= 0) return;
         if (!dev) { if (ds->allreduce_sum(buf, count, ds->allreduce_user) != 0) rc = 1; return; }
-        if (count > cap) { d_red = pool.get<double>((size_t)count); cap = count; if (!pool.ok) { rc = 1; return; } }
+        if (count > cap) { d_red = pool.alloc<double>((size_t)count); cap = count; if (!pool.ok()) { rc = 1; return; } }
         hipMemcpyAsync(d_red, buf, (size_t)count * 8, hipMemcpyHostToDevice, st);
         hipStreamSynchronize(st);
         if (ds->allreduce_sum(d_red, count, ds->allreduce_user) != 0) rc = 1;
@@ -1487,9 +1471,9 @@ struct RankSum {
         // timeout; only a rank that cannot even get those 32 bytes fails alone.
         double v[3] = {bad_range ? 1.0 : 0.0, bad_owner ? 1.0 : 0.0, 0.0};
         if (dev) {
-            d_red = pool.get<double>((size_t)cap0);
-            cap = pool.ok ? cap0 : 0;
-            if (!pool.ok) {
+            d_red = pool.alloc<double>((size_t)cap0);
+            cap = pool.ok() ? cap0 : 0;
+            if (!pool.ok()) {
                 v[2] = 1.0;
                 double* tiny = nullptr;
                 *msg = "stagei: device allocation failed before the first all-reduce (the other ranks were not joined)";
@@ -1514,7 +1498,8 @@ struct RankSum {
 struct S1Solve {
     const S1ModelView* mv; const S1PriorView* pv; const moshii_stagei_desc* ds; hipStream_t st; char* err; int errlen;
     S1Dims d; S1Ptr p;
-    DevPool pool; RankSum sum;
+    DevArena pool;     // every device allocation of one solve; freed together
+    RankSum sum;
     // frames of this rank (moshii_stagei_desc.sharded): every rank evaluates the canonical body and the attachment, the data / prior /
     // finger rows of its own frames, one rank the shared rows; normal equations and SSE are summed over the ranks through the
     // caller's all-reduce, after which every rank holds the same system and takes the same step
@@ -1589,41 +1574,41 @@ struct S1Solve {
         p.parents = mv->parents; p.vt = mv->vt; p.shapedirs = mv->shapedirs; p.posedirs = mv->posedirs; p.weights = mv->weights;
         p.Jreg = mv->Jreg; p.hands_mean = mv->hands_mean; p.comps = mv->comps; p.anc = mv->anc;
         if (pv) { p.means = pv->means; p.chols = pv->chols; p.neglogw = pv->neglogw; }
-        p.faces = pool.put(ds->faces, (size_t)3 * d.nfaces, st);
+        p.faces = pool.upload_async(ds->faces, (size_t)3 * d.nfaces, st);
         {   // vertex -> incident faces
             v2f_ptr.assign(d.V + 1, 0); v2f.resize((size_t)3 * d.nfaces);
             for (int i = 0; i < 3 * d.nfaces; ++i) v2f_ptr[ds->faces[i] + 1]++;
             for (int v = 0; v < d.V; ++v) v2f_ptr[v + 1] += v2f_ptr[v];
             std::vector<int> fill(v2f_ptr.begin(), v2f_ptr.end() - 1);
             for (int f = 0; f < d.nfaces; ++f) for (int c = 0; c < 3; ++c) v2f[fill[ds->faces[3 * f + c]]++] = f;
-            p.v2f_ptr = pool.put(v2f_ptr.data(), v2f_ptr.size(), st); p.v2f = pool.put(v2f.data(), v2f.size(), st);
+            p.v2f_ptr = pool.upload_async(v2f_ptr.data(), v2f_ptr.size(), st); p.v2f = pool.upload_async(v2f.data(), v2f.size(), st);
             hipStreamSynchronize(st);
         }
         {
             std::vector<unsigned char> ex(d.V, 0);
             for (int i = 0; i < ds->n_exclude; ++i) if (ds->exclude_vids[i] >= 0 && ds->exclude_vids[i] < d.V) ex[ds->exclude_vids[i]] = 1;
-            p.excl = pool.put(ex.data(), ex.size(), st);
+            p.excl = pool.upload_async(ex.data(), ex.size(), st);
             hipStreamSynchronize(st);
         }
-        p.obs_ids = pool.put(ds->obs_ids, ntot_obs, st); p.obs_off = pool.put(obs_off.data(), obs_off.size(), st);
-        p.obs = pool.put(ds->obs, (size_t)3 * ntot_obs, st); p.m2b = pool.put(ds->m2b, M, st);
-        p.body_ids = pool.put(ds->body_ids, d.nbody, st);
-        p.face_ids = pool.put(ds->face_ids, nface_all, st);
+        p.obs_ids = pool.upload_async(ds->obs_ids, ntot_obs, st); p.obs_off = pool.upload_async(obs_off.data(), obs_off.size(), st);
+        p.obs = pool.upload_async(ds->obs, (size_t)3 * ntot_obs, st); p.m2b = pool.upload_async(ds->m2b, M, st);
+        p.body_ids = pool.upload_async(ds->body_ids, d.nbody, st);
+        p.face_ids = pool.upload_async(ds->face_ids, nface_all, st);
         Vec wt_init_eff(ds->wt_init, ds->wt_init + M);
         if (d.nhead_rows) {
             for (int h = 0; h < d.nhead; ++h) wt_init_eff[ds->head_ids[h]] = 0.0;          // the head markers leave their per-type init rows (chmosh.py:364-367)
-            p.head_ids = pool.put(ds->head_ids, d.nhead, st); p.head_C = pool.put(ds->head_corr, (size_t)d.nhead_rows * d.nhead, st);
+            p.head_ids = pool.upload_async(ds->head_ids, d.nhead, st); p.head_C = pool.upload_async(ds->head_corr, (size_t)d.nhead_rows * d.nhead, st);
         }
-        p.wt_init = pool.put(wt_init_eff.data(), M, st);
+        p.wt_init = pool.upload_async(wt_init_eff.data(), M, st);
         hipStreamSynchronize(st);
     }
 
     // ---- work buffers and the host point
     int allocate() {
         const int F = d.F, M = d.M, nb = d.nb, NP = d.NP, K = d.K, nb1 = std::max(1, nb);
-        p.colmap = d_colmap = pool.get<int>(NP); p.finger_ids = d_finger = pool.get<int>(std::max(1, ds->n_finger));
-        p.cl0 = pool.get<int>(3 * M); p.coef0 = pool.get<double>(3 * M);
-        p.loss = pool.get<double>(3 * M); p.dinit = pool.get<double>((size_t)3 * M * nb1);
+        p.colmap = d_colmap = pool.alloc<int>(NP); p.finger_ids = d_finger = pool.alloc<int>(std::max(1, ds->n_finger));
+        p.cl0 = pool.alloc<int>(3 * M); p.coef0 = pool.alloc<double>(3 * M);
+        p.loss = pool.alloc<double>(3 * M); p.dinit = pool.alloc<double>((size_t)3 * M * nb1);
         // the evaluation point in ONE allocation (pose | trans | latent markers | betas, each part on a 128-byte boundary): one copy per trial point
         // instead of four (565 small copies a solve were ~3 ms of host time)
         pose.assign((size_t)d.NPZ * NP, 0.0); trans.assign((size_t)d.NPZ * 3, 0.0); ml.assign(3 * M, 0.0); betas.assign((size_t)nb1 * (d.per_frame ? d.NPZ : 1), 0.0);
@@ -1631,35 +1616,35 @@ struct S1Solve {
         auto up16 = [](size_t c) { return (c + 15) & ~(size_t)15; };
         pt_o_trans = up16(pose.size()); pt_o_ml = pt_o_trans + up16(trans.size()); pt_o_betas = pt_o_ml + up16(ml.size());
         hpoint.assign(pt_o_betas + up16(betas.size()), 0.0);
-        d_point = pool.get<double>(hpoint.size());
+        d_point = pool.alloc<double>(hpoint.size());
         p.pose = d_point; p.trans = d_point ? d_point + pt_o_trans : nullptr;
         p.ml = d_point ? d_point + pt_o_ml : nullptr; p.betas = d_point ? d_point + pt_o_betas : nullptr;
-        p.J0 = pool.get<double>(3 * K); p.JS = pool.get<double>((size_t)std::max(1, K * nb * 3));
-        p.fp = pool.get<double>((size_t)d.NPZ * d.P); p.Rl = pool.get<double>((size_t)d.NPZ * K * 9); p.Jl = pool.get<double>((size_t)d.NPZ * K * 9);
-        p.Rw = pool.get<double>((size_t)d.NPZ * K * 9); p.tw = pool.get<double>((size_t)d.NPZ * K * 3); p.feat = pool.get<double>((size_t)d.NPZ * d.nfeat);
-        p.om = pool.get<double>((size_t)d.NPZ * K * 9); p.Bm = pool.get<double>((size_t)d.NPZ * K * 27); p.Jb = pool.get<double>((size_t)d.NPZ * K * 3);
-        p.q = pool.get<double>((size_t)d.NPZ * K * nb1 * 3); p.featzero = pool.get<int>(d.NPZ);
-        p.can = pool.get<double>((size_t)3 * d.V); p.cl = pool.get<int>(3 * M); p.cl8 = pool.get<int>(S1_NNK * M); p.coef = pool.get<double>(3 * M); p.Fc = pool.get<double>(9 * M);
-        p.dcdb = pool.get<double>((size_t)M * 3 * nb1); p.tv = pool.get<int>(3 * M); p.sdist = pool.get<double>(M);
-        p.sdp = pool.get<double>(3 * M); p.sdabc = pool.get<double>(9 * M); p.status = pool.get<int>(4);
-        p.vlist = pool.get<int>((size_t)d.NPZ * d.ncan); p.vv = pool.get<double>((size_t)d.NPZ * d.ncan * 3);
-        p.dvs = pool.get<double>((size_t)d.NPZ * d.ncan * 3 * nb1); p.dv = pool.get<double>((size_t)F * 3 * M * 3 * d.P);
-        p.vi_T = pool.get<double>((size_t)F * 3 * M * 9); p.vi_w = pool.get<double>((size_t)F * 3 * M * S1_NWMAX);
-        p.vi_x = pool.get<double>((size_t)F * 3 * M * S1_NWMAX * 3); p.vi_n = pool.get<int>((size_t)F * 3 * M); p.vi_j = pool.get<int>((size_t)F * 3 * M * S1_NWMAX);
-        p.Lb = pool.get<double>((size_t)F * M * 36 + (size_t)F * std::max(1, d.G * d.npose_prior));
+        p.J0 = pool.alloc<double>(3 * K); p.JS = pool.alloc<double>((size_t)std::max(1, K * nb * 3));
+        p.fp = pool.alloc<double>((size_t)d.NPZ * d.P); p.Rl = pool.alloc<double>((size_t)d.NPZ * K * 9); p.Jl = pool.alloc<double>((size_t)d.NPZ * K * 9);
+        p.Rw = pool.alloc<double>((size_t)d.NPZ * K * 9); p.tw = pool.alloc<double>((size_t)d.NPZ * K * 3); p.feat = pool.alloc<double>((size_t)d.NPZ * d.nfeat);
+        p.om = pool.alloc<double>((size_t)d.NPZ * K * 9); p.Bm = pool.alloc<double>((size_t)d.NPZ * K * 27); p.Jb = pool.alloc<double>((size_t)d.NPZ * K * 3);
+        p.q = pool.alloc<double>((size_t)d.NPZ * K * nb1 * 3); p.featzero = pool.alloc<int>(d.NPZ);
+        p.can = pool.alloc<double>((size_t)3 * d.V); p.cl = pool.alloc<int>(3 * M); p.cl8 = pool.alloc<int>(S1_NNK * M); p.coef = pool.alloc<double>(3 * M); p.Fc = pool.alloc<double>(9 * M);
+        p.dcdb = pool.alloc<double>((size_t)M * 3 * nb1); p.tv = pool.alloc<int>(3 * M); p.sdist = pool.alloc<double>(M);
+        p.sdp = pool.alloc<double>(3 * M); p.sdabc = pool.alloc<double>(9 * M); p.status = pool.alloc<int>(4);
+        p.vlist = pool.alloc<int>((size_t)d.NPZ * d.ncan); p.vv = pool.alloc<double>((size_t)d.NPZ * d.ncan * 3);
+        p.dvs = pool.alloc<double>((size_t)d.NPZ * d.ncan * 3 * nb1); p.dv = pool.alloc<double>((size_t)F * 3 * M * 3 * d.P);
+        p.vi_T = pool.alloc<double>((size_t)F * 3 * M * 9); p.vi_w = pool.alloc<double>((size_t)F * 3 * M * S1_NWMAX);
+        p.vi_x = pool.alloc<double>((size_t)F * 3 * M * S1_NWMAX * 3); p.vi_n = pool.alloc<int>((size_t)F * 3 * M); p.vi_j = pool.alloc<int>((size_t)F * 3 * M * S1_NWMAX);
+        p.Lb = pool.alloc<double>((size_t)F * M * 36 + (size_t)F * std::max(1, d.G * d.npose_prior));
         const int n = mx.n, R = mx.R, fs = mx.fs, ns = mx.ns;
-        p.r = pool.get<double>(R); p.Jm = pool.get<double>((size_t)R * mx.ldn);
-        d_A = pool.get<double>((size_t)n * n); d_L = pool.get<double>((size_t)n * n);
+        p.r = pool.alloc<double>(R); p.Jm = pool.alloc<double>((size_t)R * mx.ldn);
+        d_A = pool.alloc<double>((size_t)n * n); d_L = pool.alloc<double>((size_t)n * n);
         if (want_schur) {
-            d_fcols = pool.get<int>((size_t)F * fs); d_scols = pool.get<int>(ns);
-            d_Linv = pool.get<double>((size_t)F * fs * fs); d_Y = pool.get<double>((size_t)F * fs * mx.nsp); d_z = pool.get<double>((size_t)F * fs);
-            d_T = pool.get<double>((size_t)ns * ns); d_S = pool.get<double>((size_t)ns * ns); d_h = pool.get<double>(ns); d_ds = pool.get<double>(ns);
-            d_ones = pool.get<int>((size_t)((F * fs + S1_T - 1) / S1_T) * ((ns + S1_T - 1) / S1_T));
+            d_fcols = pool.alloc<int>((size_t)F * fs); d_scols = pool.alloc<int>(ns);
+            d_Linv = pool.alloc<double>((size_t)F * fs * fs); d_Y = pool.alloc<double>((size_t)F * fs * mx.nsp); d_z = pool.alloc<double>((size_t)F * fs);
+            d_T = pool.alloc<double>((size_t)ns * ns); d_S = pool.alloc<double>((size_t)ns * ns); d_h = pool.alloc<double>(ns); d_ds = pool.alloc<double>(ns);
+            d_ones = pool.alloc<int>((size_t)((F * fs + S1_T - 1) / S1_T) * ((ns + S1_T - 1) / S1_T));
         }
-        d_dinv = pool.get<double>((size_t)(n / S1_PB + 1) * S1_PB * S1_PB); d_flags = pool.get<int>((size_t)((R + S1_T - 1) / S1_T) * ((n + S1_T - 1) / S1_T));
-        d_g = pool.get<double>(n); d_part = pool.get<double>((size_t)S1_GT_CHUNKS * n); d_vec = pool.get<double>(n);
-        d_out = pool.get<double>(std::max(n, R));
-        if (!pool.ok) return fail(MOSHII_ERR_HIP, "stagei: device allocation failed");
+        d_dinv = pool.alloc<double>((size_t)(n / S1_PB + 1) * S1_PB * S1_PB); d_flags = pool.alloc<int>((size_t)((R + S1_T - 1) / S1_T) * ((n + S1_T - 1) / S1_T));
+        d_g = pool.alloc<double>(n); d_part = pool.alloc<double>((size_t)S1_GT_CHUNKS * n); d_vec = pool.alloc<double>(n);
+        d_out = pool.alloc<double>(std::max(n, R));
+        if (!pool.ok()) return fail(MOSHII_ERR_HIP, "stagei: device allocation failed");
         hipMemsetAsync(p.status, 0, 4 * sizeof(int), st);
         return 0;
     }
@@ -1745,8 +1730,8 @@ struct S1Solve {
             hipMemcpyAsync(p.coef0, p.coef, 3 * M * 8, hipMemcpyDeviceToDevice, st);
         }
         // rigid start per frame (chmosh.py:236-238, rigid_transformations.py:39-83): Procrustes on the zero-pose markers
-        double* d_sim = pool.get<double>((size_t)3 * std::max(1, ntot_obs)); double* d_rt = pool.get<double>(6 * F);
-        if (!pool.ok) return fail(MOSHII_ERR_HIP, "stagei: device allocation failed");
+        double* d_sim = pool.alloc<double>((size_t)3 * std::max(1, ntot_obs)); double* d_rt = pool.alloc<double>(6 * F);
+        if (!pool.ok()) return fail(MOSHII_ERR_HIP, "stagei: device allocation failed");
         hipMemsetAsync(d_rt, 0, 6 * F * 8, st);
         if (nown > 0) LAUNCH(k_s1_rigid, nown, 1, S1_TPB, st, d, p, d_sim, d_rt, f_lo);
         Vec rt;
@@ -1858,8 +1843,8 @@ struct S1Solve {
         const int F = d.F, M = d.M;
         upload_point(); evaluate(0, no_prior, rows_on); fetch(r, p.r, lay.R);
         if (ds->markers_sim) {       // stagei_markers_sim_all (chmosh.py:441): every latent marker on every frame's body
-            double* d_simall = pool.get<double>((size_t)F * M * 3);
-            if (!pool.ok) return fail(MOSHII_ERR_HIP, "stagei: device allocation failed");
+            double* d_simall = pool.alloc<double>((size_t)F * M * 3);
+            if (!pool.ok()) return fail(MOSHII_ERR_HIP, "stagei: device allocation failed");
             hipMemsetAsync(d_simall, 0, (size_t)F * M * 3 * 8, st);
             if (nown > 0) LAUNCH(k_s1_simall, nown, 1, S1_TPB, st, d, p, d_simall, f_lo);
             Vec sa;

@@ -17,7 +17,7 @@ UNITS = [(os.path.join(CSRC, 'moshii_api.hip'), [], 'g++'), (os.path.join(CSRC, 
 
 
 def build(force=False, opt='-O1'):
-    deps = [u for u, _, _ in UNITS] + [os.path.join(HERE, 'fakehip', 'hip', 'hip_runtime.h'), os.path.join(CSRC, 'moshii_dev.h'), os.path.join(CSRC, 'solve_plan.h'), os.path.join(CSRC, 'stagei_plan.h'), os.path.join(CSRC, 'stagei_views.h'),
+    deps = [u for u, _, _ in UNITS] + [os.path.join(HERE, 'fakehip', 'hip', 'hip_runtime.h'), os.path.join(CSRC, 'moshii_dev.h'), os.path.join(CSRC, 'dev_mem.h'), os.path.join(CSRC, 'export_plan.h'), os.path.join(CSRC, 'solve_plan.h'), os.path.join(CSRC, 'stagei_plan.h'), os.path.join(CSRC, 'stagei_views.h'),
                                     os.path.join(ROOT, 'include', 'moshii.h')]
     if not force and os.path.exists(OUT) and all(os.path.getmtime(OUT) > os.path.getmtime(d) for d in deps):
         return OUT

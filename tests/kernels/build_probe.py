@@ -20,7 +20,7 @@ from tests.emu import build_chain_emu  # noqa: E402
 PROBE = os.path.join(HERE, 'stagei_probe.hip')
 STAGEI = os.path.join(product_build.CSRC, 'stagei.hip')
 EMU = os.path.dirname(build_chain_emu.__file__)
-DEPS = [PROBE, STAGEI, os.path.join(product_build.CSRC, 'stagei_views.h'), os.path.join(product_build.CSRC, 'stagei_plan.h'), os.path.join(ROOT, 'include', 'moshii.h')]
+DEPS = [PROBE, STAGEI, os.path.join(product_build.CSRC, 'stagei_views.h'), os.path.join(product_build.CSRC, 'stagei_plan.h'), os.path.join(product_build.CSRC, 'dev_mem.h'), os.path.join(ROOT, 'include', 'moshii.h')]
 EMU_DEPS = [os.path.join(EMU, 'fakehip', 'hip', 'hip_runtime.h'), os.path.join(EMU, 'hip_emu_runtime.cpp')]
 
 

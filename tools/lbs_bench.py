@@ -1,4 +1,5 @@
-"""Time the full-mesh LBS export kernels alone (for rocprofv3): python tools/lbs_bench.py [F] [reps] [model] [--shape E] [--repeats N]
+"""Time the full-mesh LBS export kernels alone (for rocprofv3): python tools/lbs_bench.py [F] [reps] [model] [--shape E] [--repeats N] [--f64]
+--f64: the f64 export (moshii_lbs_forward[_shape]_f64) instead of the f32 one.
 --shape E: the export with per-frame coefficients of a free shape block of E columns (moshii_lbs_forward_shape_f32) -- the body gets E
 extra shapedirs columns (a unit coefficient moves a vertex by up to 1 cm), the coefficients are N(0, 1); same poses otherwise.
 --repeats N: N timed rounds of `reps` calls each, one line per round (run-to-run spread).
@@ -267,6 +268,9 @@ if '--normals' in sys.argv:
     normals_bench(sys.argv[1:])
     sys.exit(0)
 E_SHAPE, REPEATS = 0, 1
+F64 = '--f64' in sys.argv          # time moshii_lbs_forward[_shape]_f64 instead of the f32 export
+if F64:
+    sys.argv.remove('--f64')
 for flag in ('--shape', '--repeats'):
     if flag in sys.argv:
         i = sys.argv.index(flag)
@@ -302,23 +306,24 @@ if E_SHAPE:
 sm = job['sm']
 dev = torch.device('cuda', 0)
 rng = np.random.default_rng(0)
-pose_h = rng.normal(0, 0.3, (F, sm.NP)).astype(np.float32)
+NPDT = np.float64 if F64 else np.float32
+pose_h = rng.normal(0, 0.3, (F, sm.NP)).astype(NPDT)
 if os.environ.get('LBS_HANDS') == 'still':   # a body-only Stage-II result (the reference's default): the hand-pose variables are the same in every frame
     pose_h[:, sm.body_dof:] = 0.0
 pose = torch.from_numpy(pose_h).to(dev)
-trans = torch.from_numpy(rng.normal(0, 1, (F, 3)).astype(np.float32)).to(dev)
-verts = torch.empty((F, sm.V, 3), dtype=torch.float32, device=dev)
+trans = torch.from_numpy(rng.normal(0, 1, (F, 3)).astype(NPDT)).to(dev)
+verts = torch.empty((F, sm.V, 3), dtype=torch.float64 if F64 else torch.float32, device=dev)
 stream = torch.cuda.current_stream().cuda_stream
-shape_h = rng.normal(0, 1, (F, max(E_SHAPE, 1))).astype(np.float32)
+shape_h = rng.normal(0, 1, (F, max(E_SHAPE, 1))).astype(NPDT)
 shape = torch.from_numpy(shape_h).to(dev)
 if E_SHAPE:
-    run = lambda: solver.dev.lbs_forward_device(F, pose.data_ptr(), trans.data_ptr(), verts.data_ptr(), C.c_void_p(stream), shape_ptr=shape.data_ptr())
+    run = lambda: solver.dev.lbs_forward_device(F, pose.data_ptr(), trans.data_ptr(), verts.data_ptr(), C.c_void_p(stream), shape_ptr=shape.data_ptr(), f32=not F64)
 else:
-    run = lambda: solver.dev.lbs_forward_device(F, pose.data_ptr(), trans.data_ptr(), verts.data_ptr(), C.c_void_p(stream))
+    run = lambda: solver.dev.lbs_forward_device(F, pose.data_ptr(), trans.data_ptr(), verts.data_ptr(), C.c_void_p(stream), f32=not F64)
 for _ in range(3):
     run()
 torch.cuda.synchronize()
-out_bytes = F * sm.V * 12
+out_bytes = F * sm.V * (24 if F64 else 12)
 for _ in range(REPEATS):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -327,7 +332,7 @@ for _ in range(REPEATS):
     e1.record()
     torch.cuda.synchronize()
     t = e0.elapsed_time(e1) * 1e-3 / reps
-    print(f'{mt} [{order} vertex order{", still hands" if os.environ.get("LBS_HANDS") == "still" else ""}{f", {E_SHAPE} shape coefficients" if E_SHAPE else ""}] F={F}: {t*1e6:.1f} us per call, output {out_bytes/1e6:.1f} MB -> {out_bytes/t/1e9:.0f} GB/s ({out_bytes/t/8e12*100:.1f}% of 8 TB/s), {F/t:.0f} frames/s')
+    print(f'{mt} {"f64" if F64 else "f32"} [{order} vertex order{", still hands" if os.environ.get("LBS_HANDS") == "still" else ""}{f", {E_SHAPE} shape coefficients" if E_SHAPE else ""}] F={F}: {t*1e6:.1f} us per call, output {out_bytes/1e6:.1f} MB -> {out_bytes/t/1e9:.0f} GB/s ({out_bytes/t/8e12*100:.1f}% of 8 TB/s), {F/t:.0f} frames/s')
 
 if os.environ.get('LBS_CHECK'):
     ref = solver.dev.lbs_forward(pose[:40].cpu().numpy().astype(np.float64), trans[:40].cpu().numpy().astype(np.float64),

@@ -75,7 +75,8 @@ const char* moshii_last_error(void);
  * check moshii_version() >= 101 before filling a moshii_stagei_desc declared from this header, and zero the struct first.
  * 102: moshii_solve_opts grew by the joint-angle term.  103: moshii_lbs_forward_shape_*.  104: moshii_model_set_faces,
  * moshii_vertex_normals_*, moshii_virtual_markers_* (new calls only: no struct changed).  105: moshii_surface_distance_*,
- * moshii_marker_surface_distance_* (new calls only).  106: moshii_joints_* (new calls only). */
+ * moshii_marker_surface_distance_* (new calls only).  106: moshii_joints_* (new calls only).  107: moshii_render_*,
+ * moshii_render_posed_* with the structs moshii_camera and moshii_render_opts: new calls and new structs only. */
 int  moshii_version(void);
 /* first 16 hex digits of the SHA-256 over the sources this binary was compiled from (python -m moshpp_amd.build computes the same
  * over the tree: a stale binary is detectable); "unknown" for a build outside build.py */
@@ -253,6 +254,83 @@ int moshii_joints_f32(moshii_model_t m, int32_t F, const float* pose, const floa
                       float* joints, float* rot /* or NULL */, uint32_t flags, void* stream);
 int moshii_joints_f64(moshii_model_t m, int32_t F, const double* pose, const double* trans, const double* shape /* or NULL */,
                       double* joints, double* rot /* or NULL */, uint32_t flags, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Shaded previews of solved frames (version 107): the body with observed and simulated markers, as the reference shows it while it
+ * solves (tools/visualization.py:96-130, visualize_pose_estimate), rasterised on the device so that the meshes need not leave it.
+ * ------------------------------------------------------------------------------------------- */
+
+/* RENDERING RULES.  They are the contract: the kernels (csrc/lbs_forward.hip: k_render_project, k_render_tiles) and the tests' NumPy
+ * reference (tests/render_common.py) implement exactly these.
+ *  Camera     X_c = R X_w + t (R row major, each row summed left to right); the camera looks along +z, x right, y down;
+ *             u = fx X_c.x / X_c.z + cx, v = fy X_c.y / X_c.z + cy in pixels; pixel (i, j) has its centre at (i + 0.5, j + 0.5).  All
+ *             of it in f64 whatever the input type.
+ *  Snapping   screen positions go to a 1/16-pixel grid: sx = (int)floor(16 u + 0.5), sy likewise.  A triangle is NOT DRAWN if any
+ *             vertex has X_c.z <= znear, any coordinate is non-finite, any |snapped coordinate| > 2^24, or it names a vertex twice.
+ *             THERE IS NO CLIPPING: a triangle that crosses the near plane disappears whole.
+ *  Coverage   integer edge functions (int64) at the pixel centre (16 i + 8, 16 j + 8).  Both windings are drawn: a triangle of negative
+ *             area is re-oriented first (two corners exchanged), one of zero area is dropped.  Top-left fill rule after the
+ *             re-orientation: with the oriented edge (dx, dy), E == 0 counts only where dy < 0 or (dy == 0 and dx > 0); two triangles
+ *             that share an edge cover every pixel centre on it exactly once.
+ *  Depth      perspective correct: w_k = E_k / area2, z = 1 / sum_k w_k / z_k, in f64 (any evaluation that is this algebraically, to a
+ *             few f64 roundings), rounded ONCE to f32.  The smallest f32 depth wins; ties go to the lower id.
+ *  Ids        a face carries its face id, marker k carries n_faces + k; background is -1 with depth +inf.
+ *  Markers    points[F][N][3] with a radius (metres) and a colour each: a camera-facing disc.  Pixel centres with
+ *             d^2 = (du / rx)^2 + (dv / ry)^2 <= 1 are covered, rx = fx r / z_c, ry = fy r / z_c, f64; every covered pixel gets the depth
+ *             z_c - r (f32), so a marker half sunk into the skin still shows.  A marker with a non-finite coordinate, z_c - r <= znear or
+ *             r <= 0 is skipped.
+ *  Shading    headlight, f64, one rounding.  Body: the vertex normals are those moshii_vertex_normals_* gives for the same mesh; each
+ *             is taken into camera space (R n) and kept as f32; n = sum_k (w_k / z_k) n_k normalised; a zero n gives I = ambient, else
+ *             I = ambient + (1 - ambient) max(0, -n.z); channel = floor(255 (body_rgb / 255) I + 0.5).  Marker: the same from its own
+ *             colour with I = ambient + (1 - ambient) sqrt(1 - d^2).  Background: bg_rgb.
+ *  Sampling   one sample a pixel, no anti-aliasing.  One lane owns a pixel and nothing else writes it: the result does not depend on
+ *             scheduling, two runs are bit-identical. */
+typedef struct moshii_camera {
+    double R[9];                      /* world -> camera rotation, row major */
+    double t[3];
+    double fx, fy, cx, cy;            /* pixels */
+    double znear;                     /* metres */
+} moshii_camera;
+
+typedef struct moshii_render_opts {
+    int32_t width, height;            /* 1 .. 4096 each */
+    int32_t n_cameras;                /* 1 (all frames) or F (one a frame) */
+    const moshii_camera* cameras;     /* host */
+    uint8_t body_rgb[3], bg_rgb[3];
+    double  ambient;                  /* 0 .. 1 */
+    const uint8_t* point_rgb;         /* host [N][3]; required when N > 0 */
+    const double*  point_radius;      /* host [N] metres; required when N > 0 */
+} moshii_render_opts;
+
+/* F frames of the meshes verts[F][V][3] with the handle's triangles (moshii_model_set_faces first) and the points[F][N][3] (or NULL
+ * with N == 0), seen through opts->cameras:
+ *   rgb[F][H][W][3]   8-bit colour        (or NULL)
+ *   ids[F][H][W]      the winning id      (or NULL)
+ *   depth[F][H][W]    its depth, f32      (or NULL)
+ * verts, points and the outputs are host or device pointers per flags (everything in opts is host memory and is read before the call
+ * returns); asynchronous on `stream` with MOSHII_BUFFERS_DEVICE.  The frames' normals and projected records live in the handle's
+ * scratch, a batch of frames at a time: one rendering call per handle at a time, as for moshii_virtual_markers_*.
+ * MOSHII_ERR_ARG, with moshii_last_error naming the fault: null opts or cameras; all three outputs null; a size outside 1 .. 4096;
+ * n_cameras neither 1 nor F; negative F or N; N > 0 with null points, point_rgb or point_radius; ambient outside 0 .. 1; a call before
+ * moshii_model_set_faces.  F == 0: MOSHII_OK, nothing launched. */
+int moshii_render_f32(moshii_model_t m, int32_t F, const float* verts, int32_t N, const float* points /* or NULL */,
+                      const moshii_render_opts* opts, uint8_t* rgb /* or NULL */, int32_t* ids /* or NULL */, float* depth /* or NULL */,
+                      uint32_t flags, void* stream);
+int moshii_render_f64(moshii_model_t m, int32_t F, const double* verts, int32_t N, const double* points /* or NULL */,
+                      const moshii_render_opts* opts, uint8_t* rgb /* or NULL */, int32_t* ids /* or NULL */, float* depth /* or NULL */,
+                      uint32_t flags, void* stream);
+
+/* The same of F solved frames, whose meshes never leave the device: exported into the handle's scratch a batch at a time exactly as
+ * moshii_virtual_markers_* does (same kernels, same `shape` rules, MOSHII_VM_BATCH honoured, one call per handle at a time); the
+ * batch's normals and projected records lie beside the meshes there.  Bit for bit what moshii_render_* gives on the vertices that
+ * moshii_lbs_forward[_shape]_* returns for the frames of each batch (the f32 export's roundings depend on the frames of a call: joints
+ * that stay still in it are folded into the rest positions, the shape coefficients are scaled by their largest; one batch: one call). */
+int moshii_render_posed_f32(moshii_model_t m, int32_t F, const float* pose, const float* trans, const float* shape /* or NULL */,
+                            int32_t N, const float* points /* or NULL */, const moshii_render_opts* opts, uint8_t* rgb /* or NULL */,
+                            int32_t* ids /* or NULL */, float* depth /* or NULL */, uint32_t flags, void* stream);
+int moshii_render_posed_f64(moshii_model_t m, int32_t F, const double* pose, const double* trans, const double* shape /* or NULL */,
+                            int32_t N, const double* points /* or NULL */, const moshii_render_opts* opts, uint8_t* rgb /* or NULL */,
+                            int32_t* ids /* or NULL */, float* depth /* or NULL */, uint32_t flags, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Pose prior. Replaces create_gmm_body_prior / MaxMixtureComplete
@@ -491,7 +569,7 @@ int moshii_stagei_solve(moshii_model_t m, moshii_prior_t prior /* may be NULL */
 /* Introspection for benchmarks and tests: name, dynamic-LDS bytes and workgroup size of the kernel the last moshii_chain_solve or
  * moshii_vertex_normals_* call launched ("k_vn_lds", "k_vn_gather<float>", "k_vn_gather<double>" for the latter), or the last
  * moshii_joints_* call: "k_joints<float>", "k_joints<double>", "k_joints_shape<float>", "k_joints_shape<double>" (the last two with a
- * shape row). */
+ * shape row), or the last moshii_render_* / moshii_render_posed_* call: "k_render_tiles" with its LDS bytes and 1024 threads. */
 int moshii_last_launch_info(char* kernel_name, int32_t name_cap, int32_t* lds_bytes, int32_t* block_threads);
 
 #ifdef __cplusplus

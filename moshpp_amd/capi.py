@@ -73,6 +73,35 @@ class ChunkReport(C.Structure):
                 ('max_handoff_dev', C.c_double), ('verify_tol', C.c_double)]
 
 
+class Camera(C.Structure):
+    """moshii_camera: X_c = R X_w + t (row major), u = fx X_c.x / X_c.z + cx, v = fy X_c.y / X_c.z + cy; +z forward, y down."""
+    _fields_ = [('R', C.c_double * 9), ('t', C.c_double * 3), ('fx', C.c_double), ('fy', C.c_double), ('cx', C.c_double),
+                ('cy', C.c_double), ('znear', C.c_double)]
+
+    @classmethod
+    def make(cls, R, t, fx, fy, cx, cy, znear):
+        c = cls()
+        c.R[:] = [float(x) for x in np.asarray(R, dtype=np.float64).reshape(9)]
+        c.t[:] = [float(x) for x in np.asarray(t, dtype=np.float64).reshape(3)]
+        c.fx, c.fy, c.cx, c.cy, c.znear = float(fx), float(fy), float(cx), float(cy), float(znear)
+        return c
+
+    def as_dict(self):
+        return dict(R=np.array(self.R[:]).reshape(3, 3), t=np.array(self.t[:]), fx=self.fx, fy=self.fy, cx=self.cx, cy=self.cy,
+                    znear=self.znear)
+
+
+class RenderOpts(C.Structure):
+    _fields_ = [('width', C.c_int32), ('height', C.c_int32), ('n_cameras', C.c_int32), ('cameras', C.POINTER(Camera)),
+                ('body_rgb', C.c_uint8 * 3), ('bg_rgb', C.c_uint8 * 3), ('ambient', C.c_double), ('point_rgb', _c_u8_p),
+                ('point_radius', _c_double_p)]
+
+
+_RENDER_ARGS = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(RenderOpts), C.c_void_p, C.c_void_p, C.c_void_p,
+                C.c_uint32, C.c_void_p]
+_RENDER_POSED_ARGS = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(RenderOpts), C.c_void_p,
+                      C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+
 EXPORTS = {
     # name: (restype, argtypes)
     'moshii_last_error': (C.c_char_p, []),
@@ -107,6 +136,10 @@ EXPORTS = {
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     'moshii_joints_f32': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     'moshii_joints_f64': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    'moshii_render_f32': (C.c_int, _RENDER_ARGS),
+    'moshii_render_f64': (C.c_int, _RENDER_ARGS),
+    'moshii_render_posed_f32': (C.c_int, _RENDER_POSED_ARGS),
+    'moshii_render_posed_f64': (C.c_int, _RENDER_POSED_ARGS),
     'moshii_prior_create': (C.c_int, [C.c_int32, C.c_int32, _c_double_p, _c_double_p, _c_double_p, C.POINTER(C.c_void_p)]),
     'moshii_prior_destroy': (C.c_int, [C.c_void_p]),
     'moshii_attach_create': (C.c_int, [C.c_void_p, C.c_int32, _c_int_p, _c_double_p, C.POINTER(C.c_void_p)]),
@@ -505,6 +538,131 @@ class Model:
             raise ValueError('posed_joints_device: shape_ptr given, but the model has no free shape block (set_free_shape)')
         fn = load().moshii_joints_f32 if f32 else load().moshii_joints_f64
         check(fn(self.handle, F, pose_ptr, trans_ptr, shape_ptr, out_ptr, rot_ptr, BUFFERS_DEVICE, stream))
+
+    # ---- shaded previews ----
+    def _render_opts(self, who, F, cameras, size, N, point_rgb, point_radius, body_rgb, bg_rgb, ambient):
+        """(RenderOpts, objects it points to) for F frames and N points; ValueError on what the library would refuse."""
+        try:
+            W, H = (int(x) for x in size)
+        except (TypeError, ValueError):
+            raise ValueError(f'{who}: size must be (width, height), got {size!r}')
+        if not (1 <= W <= 4096 and 1 <= H <= 4096):
+            raise ValueError(f'{who}: width and height must be within 1 .. 4096, got {W} x {H}')
+        if isinstance(cameras, Camera):
+            cameras = [cameras]
+        cameras = list(cameras)
+        if not all(isinstance(c, Camera) for c in cameras):
+            raise ValueError(f'{who}: cameras must be capi.Camera objects')
+        if len(cameras) != 1 and len(cameras) != F:
+            raise ValueError(f'{who}: one camera or one per frame ({F}), got {len(cameras)}')
+        if not 0.0 <= float(ambient) <= 1.0:
+            raise ValueError(f'{who}: ambient must be within 0 .. 1, got {ambient}')
+        o = RenderOpts()
+        cams = (Camera * len(cameras))(*cameras)
+        o.width, o.height, o.n_cameras, o.cameras = W, H, len(cameras), cams
+        o.body_rgb[:] = [int(x) for x in np.asarray(body_rgb, dtype=np.uint8).reshape(3)]
+        o.bg_rgb[:] = [int(x) for x in np.asarray(bg_rgb, dtype=np.uint8).reshape(3)]
+        o.ambient = float(ambient)
+        keep = [cams]
+        if N > 0:
+            if point_rgb is None or point_radius is None:
+                raise ValueError(f'{who}: points need point_rgb and point_radius')
+            prgb = np.asarray(point_rgb, dtype=np.uint8)
+            prgb = np.ascontiguousarray(np.broadcast_to(prgb, (N, 3)))
+            prad = np.asarray(point_radius, dtype=np.float64)
+            prad = np.ascontiguousarray(np.broadcast_to(prad, (N,)))
+            o.point_rgb = prgb.ctypes.data_as(_c_u8_p); o.point_radius = _dp(prad)
+            keep += [prgb, prad]
+        return o, keep
+
+    @staticmethod
+    def _render_outputs(F, W, H, outputs):
+        bad = set(outputs) - {'rgb', 'ids', 'depth'}
+        if bad or not outputs:
+            raise ValueError(f"render: outputs must name some of 'rgb', 'ids', 'depth', got {tuple(outputs)!r}")
+        res = {}
+        if 'rgb' in outputs:
+            res['rgb'] = np.zeros((F, H, W, 3), dtype=np.uint8)
+        if 'ids' in outputs:
+            res['ids'] = np.zeros((F, H, W), dtype=np.int32)
+        if 'depth' in outputs:
+            res['depth'] = np.zeros((F, H, W), dtype=np.float32)
+        return res
+
+    def render(self, verts, cameras, size, points=None, point_rgb=None, point_radius=None, body_rgb=(200, 170, 150), bg_rgb=(255, 255, 255),
+               ambient=0.3, outputs=('rgb', 'ids', 'depth')):
+        """Shaded previews of the meshes verts[F, V, 3] (float32 or float64, host) with the model's faces, by the rendering rules of
+        include/moshii.h: dict(rgb[F, H, W, 3] uint8, ids[F, H, W] int32, depth[F, H, W] float32) of the `outputs` asked for.
+        cameras: one capi.Camera or one per frame; size = (width, height); points[F, N, 3] with point_rgb[N, 3] (or one colour) and
+        point_radius[N] (or one radius, metres) are drawn as shaded discs, a NaN point is skipped.  ids: face id, n_faces + k for point
+        k, -1 for background (depth +inf)."""
+        self._need_faces('render')
+        verts = np.asarray(verts)
+        if verts.dtype not in (np.float32, np.float64):
+            raise ValueError(f'render: verts must be float32 or float64, not {verts.dtype}')
+        v = verts[None] if verts.ndim == 2 else verts
+        if v.ndim != 3 or v.shape[1:] != (self.V, 3):
+            raise ValueError(f'render: verts must be [F, {self.V}, 3], got {tuple(verts.shape)}')
+        v = np.ascontiguousarray(v)
+        F = v.shape[0]
+        N = 0
+        if points is not None:
+            points = self._check_points(points, F, v.dtype, 'render')
+            N = points.shape[1]
+        o, keep = self._render_opts('render', F, cameras, size, N, point_rgb, point_radius, body_rgb, bg_rgb, ambient)
+        res = self._render_outputs(F, o.width, o.height, outputs)
+        fn = load().moshii_render_f64 if v.dtype == np.float64 else load().moshii_render_f32
+        check(fn(self.handle, F, v.ctypes.data, N, points.ctypes.data if N else None, C.byref(o),
+                 *(res[k].ctypes.data if k in res else None for k in ('rgb', 'ids', 'depth')), BUFFERS_HOST, None))
+        del keep
+        return res
+
+    def render_posed(self, pose, trans, cameras, size, points=None, point_rgb=None, point_radius=None, shape=None, dtype=np.float32,
+                     body_rgb=(200, 170, 150), bg_rgb=(255, 255, 255), ambient=0.3, outputs=('rgb', 'ids', 'depth')):
+        """render() of the meshes of pose[F, NP], trans[F, 3] (shape as in lbs_forward) -- the meshes never leave the device."""
+        if dtype not in (np.float64, np.float32):
+            raise ValueError(f'render_posed: dtype must be numpy float64 or float32, not {dtype!r}')
+        self._need_faces('render_posed')
+        pose = np.ascontiguousarray(np.atleast_2d(pose), dtype=dtype)
+        trans = np.ascontiguousarray(np.atleast_2d(trans), dtype=dtype)
+        F = pose.shape[0]
+        if pose.shape != (F, self.NP) or trans.shape != (F, 3):
+            raise ValueError(f'render_posed: pose / trans must be [F, {self.NP}] / [F, 3], got {pose.shape} / {trans.shape}')
+        if shape is not None:
+            shape = self._check_shape_rows(shape, F, dtype)
+        N = 0
+        if points is not None:
+            points = self._check_points(points, F, dtype, 'render_posed')
+            N = points.shape[1]
+        o, keep = self._render_opts('render_posed', F, cameras, size, N, point_rgb, point_radius, body_rgb, bg_rgb, ambient)
+        res = self._render_outputs(F, o.width, o.height, outputs)
+        fn = load().moshii_render_posed_f64 if dtype == np.float64 else load().moshii_render_posed_f32
+        check(fn(self.handle, F, pose.ctypes.data, trans.ctypes.data, shape.ctypes.data if shape is not None else None, N,
+                 points.ctypes.data if N else None, C.byref(o), *(res[k].ctypes.data if k in res else None for k in ('rgb', 'ids', 'depth')),
+                 BUFFERS_HOST, None))
+        del keep
+        return res
+
+    def render_device(self, F, verts_ptr, cameras, size, N=0, points_ptr=None, point_rgb=None, point_radius=None, rgb_ptr=None, ids_ptr=None,
+                      depth_ptr=None, body_rgb=(200, 170, 150), bg_rgb=(255, 255, 255), ambient=0.3, stream=None, f32=True):
+        """Device buffers for verts / points / rgb / ids / depth; cameras, colours and radii are host data; asynchronous on `stream`."""
+        self._need_faces('render_device')
+        o, keep = self._render_opts('render_device', F, cameras, size, N, point_rgb, point_radius, body_rgb, bg_rgb, ambient)
+        fn = load().moshii_render_f32 if f32 else load().moshii_render_f64
+        check(fn(self.handle, F, verts_ptr, N, points_ptr, C.byref(o), rgb_ptr, ids_ptr, depth_ptr, BUFFERS_DEVICE, stream))
+        del keep
+
+    def render_posed_device(self, F, pose_ptr, trans_ptr, cameras, size, N=0, points_ptr=None, point_rgb=None, point_radius=None, rgb_ptr=None,
+                            ids_ptr=None, depth_ptr=None, body_rgb=(200, 170, 150), bg_rgb=(255, 255, 255), ambient=0.3, stream=None, f32=True,
+                            shape_ptr=None):
+        """Device buffers for pose / trans / shape / points and the outputs; asynchronous on `stream`."""
+        self._need_faces('render_posed_device')
+        if shape_ptr is not None and int(getattr(self, 'n_free_shape', 0)) <= 0:
+            raise ValueError('render_posed_device: shape_ptr given, but the model has no free shape block (set_free_shape)')
+        o, keep = self._render_opts('render_posed_device', F, cameras, size, N, point_rgb, point_radius, body_rgb, bg_rgb, ambient)
+        fn = load().moshii_render_posed_f32 if f32 else load().moshii_render_posed_f64
+        check(fn(self.handle, F, pose_ptr, trans_ptr, shape_ptr, N, points_ptr, C.byref(o), rgb_ptr, ids_ptr, depth_ptr, BUFFERS_DEVICE, stream))
+        del keep
 
     def lbs_forward_with_normals(self, pose, trans, dtype=np.float32, shape=None):
         """(verts, normals), both [F, V, 3]: the export into a device buffer, the normals from that buffer, two copies back -- the

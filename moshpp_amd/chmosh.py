@@ -286,6 +286,63 @@ class StageIISolver:
             self.dev.set_faces(self.sm.f)
         return self.dev.marker_surface_distance(out['pose'], out['trans'], points, shape=out['shape'] if self.n_shape else None, dtype=dtype)
 
+    def render(self, out, obs=None, vis=None, camera=None, size=(512, 512), view='front', frame_ids=None, marker_radius=0.0095, labels=None,
+               up='z', dtype=np.float32):
+        """Shaded previews of a solve() result, what the reference shows while it solves (tools/visualization.py:96-130): the body, the
+        observed markers in one colour and the solve's simulated markers out['markers_sim'] in another, rasterised on the solver's own
+        handle by the rendering rules of include/moshii.h -- the meshes stay on the device.  dict(rgb[F, H, W, 3] uint8, ids[F, H, W],
+        depth[F, H, W], camera, n_observed): ids hold the face id, n_faces + k for observed marker k, n_faces + n_observed + k for
+        simulated marker k, -1 for background.
+        The observations as in marker_skin_distance: obs[F, M, 3] (and vis[F, M]), or the ragged out['markers_obs'] / out['labels_obs']
+        laid out over `labels`; an unobserved marker (NaN) is not drawn; without either only the simulated markers are.  camera: a
+        capi.Camera; default preview.preview_camera of the rendered frames' joints from `view` with the world axis `up` upwards.
+        size = (width, height); frame_ids: rows of the result (default: all)."""
+        from . import preview
+        for k in ('pose', 'trans') + (('shape',) if self.n_shape else ()):
+            if k not in out:
+                raise KeyError(f"StageIISolver.render: the result has no '{k}'")
+        if getattr(self.sm, 'f', None) is None:
+            raise ValueError('StageIISolver.render: the surface model has no faces (f)')
+        pose, trans = np.atleast_2d(out['pose']), np.atleast_2d(out['trans'])
+        F = pose.shape[0]
+        if obs is not None:
+            points = np.array(obs, dtype=np.float64)
+            if vis is not None:
+                points[~np.asarray(vis, dtype=bool)] = np.nan
+        elif 'markers_obs' in out and 'labels_obs' in out:
+            if labels is None:
+                raise ValueError('StageIISolver.render: the ragged markers_obs / labels_obs need the label order (labels)')
+            points = pack_observed_markers(out['markers_obs'], out['labels_obs'], labels)
+        else:
+            points = np.zeros((F, 0, 3))
+        if points.ndim != 3 or points.shape[0] != F or points.shape[2] != 3:
+            raise ValueError(f'StageIISolver.render: the observations are {points.shape}, the result has {F} frames')
+        n_obs = points.shape[1]
+        sim = np.asarray(out['markers_sim'], dtype=np.float64) if 'markers_sim' in out else np.zeros((F, 0, 3))
+        if sim.ndim != 3 or sim.shape[0] != F or sim.shape[2] != 3:
+            raise ValueError(f'StageIISolver.render: markers_sim is {sim.shape}, the result has {F} frames')
+        ids = np.arange(F) if frame_ids is None else np.atleast_1d(np.asarray(frame_ids))
+        if ids.ndim != 1 or (len(ids) and not np.issubdtype(ids.dtype, np.integer)):
+            raise ValueError('StageIISolver.render: frame_ids must be a list of integers')
+        if len(ids) and (ids.min() < 0 or ids.max() >= F):
+            raise IndexError(f'StageIISolver.render: frame_ids outside the {F} solved frames')
+        if not float(marker_radius) > 0.0:
+            raise ValueError(f'StageIISolver.render: marker_radius must be positive, got {marker_radius!r}')
+        shape = np.atleast_2d(out['shape'])[ids] if self.n_shape else None
+        if camera is None:
+            if len(ids) == 0:
+                raise ValueError('StageIISolver.render: no frame to frame a camera on; pass a camera')
+            camera = preview.preview_camera(self.dev.posed_joints(pose[ids], trans[ids], shape=shape), size, view=view, up=up)
+        if not getattr(self.dev, 'n_faces', 0):
+            self.dev.set_faces(self.sm.f)
+        allp = np.concatenate([points, sim], axis=1)[ids]
+        N = allp.shape[1]
+        prgb = np.array([preview.OBSERVED_RGB] * n_obs + [preview.SIMULATED_RGB] * (N - n_obs), dtype=np.uint8).reshape(N, 3)
+        res = self.dev.render_posed(pose[ids], trans[ids], camera, size, points=allp if N else None, point_rgb=prgb if N else None,
+                                    point_radius=float(marker_radius) if N else None, shape=shape, dtype=dtype)
+        res.update(camera=camera, n_observed=n_obs)
+        return res
+
 
 def pack_observed_markers(markers_obs, labels_obs, labels, frame_ids=None):
     """points[T, M, 3]: the per-frame ragged lists a Stage-II result stores (markers_obs[f][j] is the marker labels_obs[f][j]) laid out

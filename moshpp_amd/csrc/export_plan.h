@@ -40,4 +40,36 @@ inline Batch plan_batch(size_t frame_bytes, long long F, long long items, bool i
     return b;
 }
 
+// moshii_render_* / moshii_render_posed_*: a batch of frames is rendered from
+//   [meshes of a batch (posed call only) | their vertex normals | V projected records a frame | N marker records a frame |
+//    the cameras | N radii (double) | N colours (3 bytes)]
+// every part on a 16-byte boundary.  The cameras, radii and colours are the call's, not the batch's.
+struct RenderBatch {
+    long long batch = 0;
+    size_t off_normals = 0, off_rec = 0, off_mrec = 0, off_cams = 0, off_radius = 0, off_prgb = 0, bytes = 0;
+};
+constexpr size_t kRenderVertexBytes = 32, kRenderMarkerBytes = 40, kCameraBytes = 17 * sizeof(double);
+
+// frame_bytes: one mesh (= one frame of normals); F >= 1 frames of V vertices and N >= 0 points, n_cameras cameras; posed: the meshes
+// are exported into the scratch as well; override_batch: MOSHII_VM_BATCH, 0 = unset.
+// Frames per batch: 256 MB of meshes, normals and records; whole 128-frame tiles where it reaches one; no more than F; no more than
+// 65 535 (the frames of a batch are the tile kernel's grid.z and the f64 export's grid.y).
+inline RenderBatch plan_render(size_t frame_bytes, long long F, long long V, long long N, long long n_cameras, bool posed, int override_batch) {
+    RenderBatch b;
+    const size_t per_frame = (posed ? 2 : 1) * frame_bytes + (size_t)V * kRenderVertexBytes + (size_t)N * kRenderMarkerBytes;
+    long long batch = std::max<long long>(1, (long long)(kMeshBudget / per_frame));
+    if (batch >= kFrameTile) batch = batch / kFrameTile * kFrameTile;
+    if (override_batch > 0) batch = override_batch;
+    batch = std::min<long long>(std::min<long long>(batch, F), kGridY);
+    b.batch = batch;
+    b.off_normals = posed ? align16((size_t)batch * frame_bytes) : 0;
+    b.off_rec = align16(b.off_normals + (size_t)batch * frame_bytes);
+    b.off_mrec = align16(b.off_rec + (size_t)batch * (size_t)V * kRenderVertexBytes);
+    b.off_cams = align16(b.off_mrec + (size_t)batch * (size_t)N * kRenderMarkerBytes);
+    b.off_radius = align16(b.off_cams + (size_t)n_cameras * kCameraBytes);
+    b.off_prgb = align16(b.off_radius + (size_t)N * sizeof(double));
+    b.bytes = b.off_prgb + (size_t)N * 3;
+    return b;
+}
+
 }  // namespace export_plan

@@ -1449,6 +1449,246 @@ __global__ __launch_bounds__(64 * JT_WAVES) void k_joints(ModelDev md, int F, co
     }
 }
 
+// ---- shaded previews of exported meshes (moshii_render_*, moshii_render_posed_*) --------------------------------------------------
+// What the reference shows while it solves (tools/visualization.py:96-130: the body with observed and simulated markers), rasterised
+// here by the rules of include/moshii.h ("Rendering rules"): pinhole camera in f64, screen positions snapped to a 1/16-pixel grid,
+// integer edge functions with the top-left rule, perspective-correct depth rounded once to f32, smallest depth wins, ties to the
+// lower id, markers as camera-facing discs, headlight shading.  Two kernels:
+//   k_render_project<T>  per (frame, vertex): camera-space depth, snapped position, camera-space normal -> one 32-byte RenderVertex;
+//                        per (frame, marker): centre, half axes, depth -> one RenderMarker.  The only kernel that reads T.
+//   k_render_tiles       ONE WORKGROUP OF 1024 LANES OWNS ONE 32 x 32 TILE OF ONE FRAME, one lane one pixel, the pixel's best
+//                        (depth, id) in the lane's registers.  Nothing is ever written to the image but the owner's final store: no
+//                        atomics on the image, so no order of arrival exists and two runs give the same bits.
+// The workgroup walks the items (faces 0 .. NF - 1, then markers NF .. NF + N - 1) RD_CHUNK at a time: every lane takes one item, tests
+// its snapped bounding box against the tile's pixel centres, and the survivors are compacted into an LDS list (ballot + popcount prefix
+// within the wave, one LDS atomicAdd a wave for the wave's base: the list's order is arbitrary, the tie rule makes it irrelevant).  The
+// lane that found a survivor also writes its set-up, once per tile: the three edge functions at the tile's first pixel centre (int64,
+// the fill-rule bias folded in), their steps per pixel, and q_k = 1 / (z_k area2), so that a covered pixel's depth is
+// 1 / (E_0 q_0 + E_1 q_1 + E_2 q_2).  After a barrier every lane runs the list; all lanes read the same entry (an LDS broadcast).
+// LDS: 76 bytes an entry in four arrays, 77 840 bytes for 1024 entries + the two counters: two workgroups would fit the 160 KB of a CU;
+// at 76 VGPRs (6 waves a SIMD, a workgroup takes 4) the registers admit one.
+// A body far away (all faces in one tile) costs NF / 1024 chunks of 1024 entries in that one workgroup; a few huge triangles cost one
+// short list in every workgroup.  The lanes of a partial tile outside the image take part in everything but the final store.
+#define RD_TILE 32
+#define RD_THREADS (RD_TILE * RD_TILE)
+#define RD_CHUNK 1024
+#define RD_LDS_BYTES (RD_CHUNK * 76 + 16)
+#define RD_SNAP_MAX 16777216.0   // 2^24
+
+// X_c = R X + t, row major, summed left to right
+__device__ __forceinline__ void rd_to_camera(const moshii_camera& c, double x, double y, double z, double* o) {
+#pragma clang fp contract(off)
+    o[0] = c.R[0] * x + c.R[1] * y + c.R[2] * z + c.t[0];
+    o[1] = c.R[3] * x + c.R[4] * y + c.R[5] * z + c.t[1];
+    o[2] = c.R[6] * x + c.R[7] * y + c.R[8] * z + c.t[2];
+}
+__device__ __forceinline__ bool rd_finite(double x) { return x - x == 0.0; }
+
+template <class T>
+__global__ __launch_bounds__(256) void k_render_project(int V, int N, int nf, int cam_stride, const moshii_camera* __restrict__ cams,
+                                                        const T* __restrict__ verts, const T* __restrict__ normals,
+                                                        const T* __restrict__ points, const double* __restrict__ radius,
+                                                        RenderVertex* __restrict__ rec, RenderMarker* __restrict__ mrec) {
+#pragma clang fp contract(off)
+    const int item = blockIdx.x * blockDim.x + threadIdx.x;
+    if (item >= V + N) return;
+    for (int f = blockIdx.y; f < nf; f += gridDim.y) {
+        const moshii_camera& c = cams[(size_t)f * cam_stride];
+        if (item < V) {
+            const T* p = verts + ((size_t)f * V + item) * 3;
+            const T* n = normals + ((size_t)f * V + item) * 3;
+            double xc[3];
+            rd_to_camera(c, (double)p[0], (double)p[1], (double)p[2], xc);
+            RenderVertex r;
+            r.sx = 0; r.sy = 0; r.z = xc[2]; r.ok = 0;
+            const double nx = (double)n[0], ny = (double)n[1], nz = (double)n[2];
+            r.n[0] = (float)(c.R[0] * nx + c.R[1] * ny + c.R[2] * nz);
+            r.n[1] = (float)(c.R[3] * nx + c.R[4] * ny + c.R[5] * nz);
+            r.n[2] = (float)(c.R[6] * nx + c.R[7] * ny + c.R[8] * nz);
+            if (rd_finite(xc[0]) && rd_finite(xc[1]) && rd_finite(xc[2]) && xc[2] > c.znear) {
+                const double u = c.fx * xc[0] / xc[2] + c.cx, v = c.fy * xc[1] / xc[2] + c.cy;
+                const double su = floor(16.0 * u + 0.5), sv = floor(16.0 * v + 0.5);
+                if (rd_finite(su) && rd_finite(sv) && fabs(su) <= RD_SNAP_MAX && fabs(sv) <= RD_SNAP_MAX) { r.sx = (int)su; r.sy = (int)sv; r.ok = 1; }
+            }
+            rec[(size_t)f * V + item] = r;
+        } else {
+            const int k = item - V;
+            const T* p = points + ((size_t)f * N + k) * 3;
+            const double rad = radius[k];
+            double xc[3];
+            rd_to_camera(c, (double)p[0], (double)p[1], (double)p[2], xc);
+            RenderMarker m;
+            m.uc = 0.0; m.vc = 0.0; m.rx = 0.0; m.ry = 0.0; m.depth = 0.0f; m.ok = 0;
+            if (rd_finite(xc[0]) && rd_finite(xc[1]) && rd_finite(xc[2]) && rad > 0.0 && xc[2] - rad > c.znear) {
+                m.uc = c.fx * xc[0] / xc[2] + c.cx; m.vc = c.fy * xc[1] / xc[2] + c.cy;
+                m.rx = c.fx * rad / xc[2]; m.ry = c.fy * rad / xc[2];
+                m.depth = (float)(xc[2] - rad);
+                m.ok = rd_finite(m.uc) && rd_finite(m.vc) && m.rx > 0.0 && m.ry > 0.0 && rd_finite(m.rx) && rd_finite(m.ry);
+            }
+            mrec[(size_t)f * N + k] = m;
+        }
+    }
+}
+
+// A face's set-up relative to the pixel centre (ox, oy) (1/16-pixel units).  v0 .. v2: its vertices' records; a face of negative area
+// is re-oriented by exchanging v1 and v2, so that e, q and the caller's records all speak of the same corners afterwards.
+//   e[k]   the edge function opposite corner k at (ox, oy): positive inside, e[k] / area2 is corner k's barycentric weight
+//   a[k], b[k]   its steps per PIXEL in x and y
+//   q[k]   1 / (z_k area2)
+// false: the face is not drawn (a vertex not ok, a vertex named twice, no area).
+struct RdFace { long long e[3]; int a[3], b[3]; double q[3]; };
+__device__ __forceinline__ void rd_edge(const RenderVertex& pa, const RenderVertex& pb, const RenderVertex& pk, int ox, int oy, long long area2,
+                                        int k, RdFace* s) {
+#pragma clang fp contract(off)
+    const int dx = pb.sx - pa.sx, dy = pb.sy - pa.sy;
+    s->e[k] = (long long)dx * (oy - pa.sy) - (long long)dy * (ox - pa.sx);
+    s->a[k] = -16 * dy; s->b[k] = 16 * dx;
+    s->q[k] = 1.0 / pk.z / (double)area2;
+}
+__device__ __forceinline__ bool rd_face_setup(unsigned ia, unsigned ib, unsigned ic, RenderVertex& v0, RenderVertex& v1, RenderVertex& v2,
+                                              int ox, int oy, RdFace* s) {
+    if (ia == ib || ib == ic || ia == ic) return false;
+    if (!(v0.ok && v1.ok && v2.ok)) return false;
+    long long area2 = (long long)(v1.sx - v0.sx) * (v2.sy - v0.sy) - (long long)(v1.sy - v0.sy) * (v2.sx - v0.sx);
+    if (area2 == 0) return false;
+    if (area2 < 0) { const RenderVertex t = v1; v1 = v2; v2 = t; area2 = -area2; }
+    rd_edge(v1, v2, v0, ox, oy, area2, 0, s);
+    rd_edge(v2, v0, v1, ox, oy, area2, 1, s);
+    rd_edge(v0, v1, v2, ox, oy, area2, 2, s);
+    return true;
+}
+// the fill rule's bias of an edge with steps (a, b): 0 on a top or left edge (E == 0 is inside), -1 elsewhere
+__device__ __forceinline__ int rd_bias(int a, int b) { return (a > 0 || (a == 0 && b > 0)) ? 0 : -1; }
+
+// the lane's share of a marker: d^2 = (du / rx)^2 + (dv / ry)^2 at the pixel centre (i + 0.5, j + 0.5)
+__device__ __forceinline__ double rd_disc(double uc, double vc, double rx, double ry, int i, int j) {
+#pragma clang fp contract(off)
+    const double tx = ((double)i + 0.5 - uc) / rx, ty = ((double)j + 0.5 - vc) / ry;
+    return tx * tx + ty * ty;
+}
+
+__global__ __launch_bounds__(RD_THREADS) void k_render_tiles(RenderArgs A) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+    long long* s_e = reinterpret_cast<long long*>(lds_raw);                       // [3][RD_CHUNK]  face: e[k] + bias; marker: uc, vc, rx
+    double* s_q = reinterpret_cast<double*>(lds_raw + RD_CHUNK * 24);             // [3][RD_CHUNK]  face: q[k]; marker: ry
+    int* s_ab = reinterpret_cast<int*>(lds_raw + RD_CHUNK * 48);                  // [6][RD_CHUNK]  face: a[k], b[k]; marker: the depth's bits
+    int* s_id = reinterpret_cast<int*>(lds_raw + RD_CHUNK * 72);                  // [RD_CHUNK]
+    int* s_cnt = reinterpret_cast<int*>(lds_raw + RD_CHUNK * 76);                 // [2]: chunk c counts in s_cnt[c & 1]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int px = tid & (RD_TILE - 1), py = tid / RD_TILE;
+    const int tx0 = blockIdx.x * RD_TILE, ty0 = blockIdx.y * RD_TILE;
+    const int pi = tx0 + px, pj = ty0 + py;
+    const size_t f = blockIdx.z;
+    const int ox = 16 * tx0 + 8, oy = 16 * ty0 + 8, span = 16 * (RD_TILE - 1);   // the tile's pixel centres: ox .. ox + span
+    const RenderVertex* rec = A.rec + f * A.V;
+    const RenderMarker* mrec = A.mrec + f * A.N;
+    const int nitems = A.NF + A.N;
+    float best = __builtin_inff();
+    int bid = -1;
+    if (tid < 2) s_cnt[tid] = 0;
+    __syncthreads();
+    for (int base = 0, c = 0; base < nitems; base += RD_CHUNK, c ^= 1) {
+        const int item = base + tid;
+        bool keep = false;
+        RdFace fs;
+        RenderMarker mk;
+        if (item < A.NF) {
+            unsigned ia, ib, ic;
+            sd_face_ids(A.tris, A.w16 != 0, (unsigned)item, &ia, &ib, &ic);
+            RenderVertex v0 = rec[ia], v1 = rec[ib], v2 = rec[ic];
+            const int x0 = min(min(v0.sx, v1.sx), v2.sx), x1 = max(max(v0.sx, v1.sx), v2.sx);
+            const int y0 = min(min(v0.sy, v1.sy), v2.sy), y1 = max(max(v0.sy, v1.sy), v2.sy);
+            keep = rd_face_setup(ia, ib, ic, v0, v1, v2, ox, oy, &fs) && x1 >= ox && x0 <= ox + span && y1 >= oy && y0 <= oy + span;
+        } else if (item < nitems) {
+            mk = mrec[item - A.NF];
+            // (1e-6 pixel of slack: the bounds are rounded sums, the pixel test below is the rule)
+            keep = mk.ok && mk.uc + mk.rx + 1e-6 >= (double)tx0 + 0.5 && mk.uc - mk.rx - 1e-6 <= (double)tx0 + (RD_TILE - 0.5) &&
+                   mk.vc + mk.ry + 1e-6 >= (double)ty0 + 0.5 && mk.vc - mk.ry - 1e-6 <= (double)ty0 + (RD_TILE - 0.5);
+        }
+        const unsigned long long bal = __ballot(keep);
+        int wbase = 0;
+        if (lane == 0) wbase = atomicAdd(&s_cnt[c], __popcll(bal));
+        wbase = __shfl(wbase, 0);
+        if (keep) {
+            const int slot = wbase + __popcll(bal & ((1ull << lane) - 1ull));
+            s_id[slot] = item;
+            if (item < A.NF) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    s_e[k * RD_CHUNK + slot] = fs.e[k] + rd_bias(fs.a[k], fs.b[k]);
+                    s_q[k * RD_CHUNK + slot] = fs.q[k];
+                    s_ab[k * RD_CHUNK + slot] = fs.a[k];
+                    s_ab[(3 + k) * RD_CHUNK + slot] = fs.b[k];
+                }
+            } else {
+                s_e[slot] = __builtin_bit_cast(long long, mk.uc);
+                s_e[RD_CHUNK + slot] = __builtin_bit_cast(long long, mk.vc);
+                s_e[2 * RD_CHUNK + slot] = __builtin_bit_cast(long long, mk.rx);
+                s_q[slot] = mk.ry;
+                s_ab[slot] = __builtin_bit_cast(int, mk.depth);
+            }
+        }
+        if (tid == 0) s_cnt[c ^ 1] = 0;   // (the next chunk's counter: nobody touches it before the barrier after this chunk's run)
+        __syncthreads();
+        const int cnt = s_cnt[c];
+        for (int s = 0; s < cnt; ++s) {
+            const int id = s_id[s];
+            float z;
+            if (id < A.NF) {
+                const int a0 = s_ab[s], a1 = s_ab[RD_CHUNK + s], a2 = s_ab[2 * RD_CHUNK + s];
+                const int b0 = s_ab[3 * RD_CHUNK + s], b1 = s_ab[4 * RD_CHUNK + s], b2 = s_ab[5 * RD_CHUNK + s];
+                const long long e0 = s_e[s] + (long long)a0 * px + (long long)b0 * py;
+                const long long e1 = s_e[RD_CHUNK + s] + (long long)a1 * px + (long long)b1 * py;
+                const long long e2 = s_e[2 * RD_CHUNK + s] + (long long)a2 * px + (long long)b2 * py;
+                if ((e0 | e1 | e2) < 0) continue;
+                const double den = (double)(e0 - rd_bias(a0, b0)) * s_q[s] + (double)(e1 - rd_bias(a1, b1)) * s_q[RD_CHUNK + s] +
+                                   (double)(e2 - rd_bias(a2, b2)) * s_q[2 * RD_CHUNK + s];
+                z = (float)(1.0 / den);
+            } else {
+                const double d2 = rd_disc(__builtin_bit_cast(double, s_e[s]), __builtin_bit_cast(double, s_e[RD_CHUNK + s]),
+                                          __builtin_bit_cast(double, s_e[2 * RD_CHUNK + s]), s_q[s], pi, pj);
+                if (!(d2 <= 1.0)) continue;
+                z = __builtin_bit_cast(float, s_ab[s]);
+            }
+            if (z < best || (z == best && id < bid)) { best = z; bid = id; }
+        }
+        __syncthreads();
+    }
+    if (pi >= A.W || pj >= A.H) return;
+    const size_t at = (f * A.H + pj) * A.W + pi;
+    if (A.ids) A.ids[at] = bid;
+    if (A.depth) A.depth[at] = best;
+    if (!A.rgb) return;
+    double inten = A.ambient;
+    const unsigned char* col = A.bg;
+    if (bid >= A.NF) {
+        const RenderMarker mk = mrec[bid - A.NF];
+        const double d2 = rd_disc(mk.uc, mk.vc, mk.rx, mk.ry, pi, pj);
+        inten = A.ambient + (1.0 - A.ambient) * sqrt(fmax(0.0, 1.0 - d2));
+        col = A.prgb + 3 * (size_t)(bid - A.NF);
+    } else if (bid >= 0) {
+        unsigned ia, ib, ic;
+        sd_face_ids(A.tris, A.w16 != 0, (unsigned)bid, &ia, &ib, &ic);
+        RenderVertex v0 = rec[ia], v1 = rec[ib], v2 = rec[ic];
+        RdFace fs;
+        rd_face_setup(ia, ib, ic, v0, v1, v2, 16 * pi + 8, 16 * pj + 8, &fs);
+        const double b0 = (double)fs.e[0] * fs.q[0], b1 = (double)fs.e[1] * fs.q[1], b2 = (double)fs.e[2] * fs.q[2];   // a corner's weight over its depth
+        double n[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) n[i] = b0 * (double)v0.n[i] + b1 * (double)v1.n[i] + b2 * (double)v2.n[i];
+        const double l2 = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
+        if (l2 > 0.0 && rd_finite(l2)) inten = A.ambient + (1.0 - A.ambient) * fmax(0.0, -(n[2] / sqrt(l2)));
+        col = A.body;
+    }
+    unsigned char* o = A.rgb + at * 3;
+    if (bid < 0) { o[0] = col[0]; o[1] = col[1]; o[2] = col[2]; }
+    else {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) o[i] = (unsigned char)floor(255.0 * ((double)col[i] / 255.0) * inten + 0.5);
+    }
+}
+
 }  // namespace
 
 static void free_ptr(void* p) { if (p) hipFree(p); }
@@ -1963,4 +2203,32 @@ extern "C" hipError_t moshii_launch_joints(hipStream_t stream, const ModelDev* m
     if (which) *which = f64 ? (shape ? "k_joints_shape<double>" : "k_joints<double>") : (shape ? "k_joints_shape<float>" : "k_joints<float>");
     if (f64) return joints_launch<double>(stream, *md, F, (const double*)pose, (const double*)trans, (const double*)shape, (double*)joints, (double*)rot);
     return joints_launch<float>(stream, *md, F, (const float*)pose, (const float*)trans, (const float*)shape, (float*)joints, (float*)rot);
+}
+
+// ---- shaded previews: launches (the handle, the scratch layout and the checks live in moshii_api.hip) ----
+// nf frames (at most 65 535: grid.z): project the vertices and markers of every frame, then one workgroup a tile and frame.  args->rec /
+// args->mrec receive the records; cams on the device, cam_stride 0 (one camera for all frames) or 1; points / radius null when N == 0.
+// *which, *lds_bytes, *threads: k_render_tiles for moshii_last_launch_info.
+extern "C" hipError_t moshii_launch_render(hipStream_t stream, int nf, int f64, const void* verts, const void* normals, const void* points,
+                                           const double* radius, const moshii_camera* cams, int cam_stride, const RenderArgs* args,
+                                           const char** which, int* lds_bytes, int* threads) {
+    if (which) *which = "";
+    if (lds_bytes) *lds_bytes = 0;
+    if (threads) *threads = RD_THREADS;
+    if (nf <= 0) return hipSuccess;
+    const RenderArgs& A = *args;
+    const dim3 pgrid((unsigned)((A.V + A.N + 255) / 256), (unsigned)std::min(nf, 1024));
+    RenderVertex* rec = const_cast<RenderVertex*>(A.rec);
+    RenderMarker* mrec = const_cast<RenderMarker*>(A.mrec);
+    if (f64) hipLaunchKernelGGL(k_render_project<double>, pgrid, dim3(256), 0, stream, A.V, A.N, nf, cam_stride, cams, (const double*)verts, (const double*)normals, (const double*)points, radius, rec, mrec);
+    else hipLaunchKernelGGL(k_render_project<float>, pgrid, dim3(256), 0, stream, A.V, A.N, nf, cam_stride, cams, (const float*)verts, (const float*)normals, (const float*)points, radius, rec, mrec);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_render_tiles), hipFuncAttributeMaxDynamicSharedMemorySize, RD_LDS_BYTES);   // (the opt-in above 64 KB)
+    if (e != hipSuccess) return e;
+    if (which) *which = "k_render_tiles";
+    if (lds_bytes) *lds_bytes = RD_LDS_BYTES;
+    const dim3 tgrid((unsigned)((A.W + RD_TILE - 1) / RD_TILE), (unsigned)((A.H + RD_TILE - 1) / RD_TILE), (unsigned)nf);
+    hipLaunchKernelGGL(k_render_tiles, tgrid, dim3(RD_THREADS), RD_LDS_BYTES, stream, A);
+    return hipGetLastError();
 }

@@ -37,6 +37,9 @@ extern "C" hipError_t moshii_launch_surface_distance(hipStream_t stream, int V, 
                                                      const char** which, int* lds_bytes, int* threads);
 extern "C" hipError_t moshii_launch_joints(hipStream_t stream, const ModelDev* md, int F, int f64, const void* pose, const void* trans,
                                            const void* shape, void* joints, void* rot, const char** which, int* threads);
+extern "C" hipError_t moshii_launch_render(hipStream_t stream, int nf, int f64, const void* verts, const void* normals, const void* points,
+                                           const double* radius, const moshii_camera* cams, int cam_stride, const RenderArgs* args,
+                                           const char** which, int* lds_bytes, int* threads);
 
 namespace {
 
@@ -372,7 +375,7 @@ void note_launch(const std::string& name, int lds, int threads) {
 extern "C" {
 
 const char* moshii_last_error(void) { return g_err.c_str(); }
-int moshii_version(void) { return 106; }   // 101: moshii_stagei_desc grew by init_sq; 102: moshii_solve_opts by the joint-angle term; 103: moshii_lbs_forward_shape_*; 104: moshii_model_set_faces, moshii_vertex_normals_*, moshii_virtual_markers_*; 105: moshii_surface_distance_*, moshii_marker_surface_distance_*; 106: moshii_joints_* (include/moshii.h)
+int moshii_version(void) { return 107; }   // 101: moshii_stagei_desc grew by init_sq; 102: moshii_solve_opts by the joint-angle term; 103: moshii_lbs_forward_shape_*; 104: moshii_model_set_faces, moshii_vertex_normals_*, moshii_virtual_markers_*; 105: moshii_surface_distance_*, moshii_marker_surface_distance_*; 106: moshii_joints_*; 107: moshii_render_*, moshii_render_posed_* (include/moshii.h)
 #ifndef MOSHII_SRC_HASH
 #define MOSHII_SRC_HASH "unknown"
 #endif
@@ -768,7 +771,113 @@ static int joints_impl(moshii_model_t m, int32_t F, const T* pose, const T* tran
     return MOSHII_OK;
 }
 
+// ---- shaded previews (version 107) ----
+namespace {
+const char* render_check(moshii_model_t m, int32_t F, int32_t N, const void* points, const moshii_render_opts* o, const void* rgb,
+                         const void* ids, const void* depth) {
+    if (!m) return "null model";
+    if (F < 0 || N < 0) return "negative F or N";
+    if (!o) return "opts is null";
+    if (!o->cameras) return "opts->cameras is null";
+    if (!rgb && !ids && !depth) return "rgb, ids and depth are all null";
+    if (o->width < 1 || o->width > 4096 || o->height < 1 || o->height > 4096) return "width and height must be within 1 .. 4096";
+    if (o->n_cameras != 1 && o->n_cameras != F) return "n_cameras must be 1 or F";
+    if (N > 0 && (!points || !o->point_rgb || !o->point_radius)) return "N > 0 needs points, point_rgb and point_radius";
+    if (!(o->ambient >= 0.0 && o->ambient <= 1.0)) return "ambient must be within 0 .. 1";
+    return nullptr;
+}
+}  // namespace
+
+// Both entries: a batch of frames at a time from the handle's scratch (export_plan.h: plan_render) -- the batch's vertex normals (the
+// kernels of moshii_vertex_normals_*), its projected records, then one workgroup a tile and frame.  verts: the caller's meshes
+// (moshii_render_*), or null and pose / trans / shape, exported into the scratch first as moshii_virtual_markers_* does.
+template <class T>
+static int render_impl(moshii_model_t m, int32_t F, const T* verts, const T* pose, const T* trans, const T* shape, bool posed, int32_t N,
+                       const T* points, const moshii_render_opts* o, uint8_t* rgb, int32_t* ids, float* depth, uint32_t flags, void* stream_,
+                       const char* name) {
+    if (const char* bad = render_check(m, F, N, points, o, rgb, ids, depth)) return fail(MOSHII_ERR_ARG, std::string(name) + ": " + bad);
+    if (posed) if (int rc = need_shape_block(m, shape)) return rc;
+    if (int rc = need_faces(m, name)) return rc;
+    if ((long long)m->n_faces + N > 0x7fffffffLL) return fail(MOSHII_ERR_UNSUPPORTED, std::string(name) + ": faces + points beyond the 31 bits of an id");
+    if (F == 0) return MOSHII_OK;
+    if (posed ? (!pose || !trans) : !verts) return fail(MOSHII_ERR_ARG, std::string(name) + (posed ? ": pose or trans is null" : ": verts is null"));
+    hipStream_t stream = (hipStream_t)stream_;
+    if (posed) if (int rc = need_l32<T>(m)) return rc;
+    const int V = m->V, W = o->width, H = o->height;
+    const size_t frame_bytes = (size_t)V * 3 * sizeof(T);
+    const export_plan::RenderBatch bp = export_plan::plan_render(frame_bytes, F, V, N, o->n_cameras, posed, batch_override());
+    if (int rc = m->vmscratch.reserve(bp.bytes)) return rc;   // (waits for the call before this one)
+    char* base = m->vmscratch.ptr;
+    T* d_mesh = reinterpret_cast<T*>(base);
+    T* d_normals = reinterpret_cast<T*>(base + bp.off_normals);
+    moshii_camera* d_cams = reinterpret_cast<moshii_camera*>(base + bp.off_cams);
+    double* d_radius = reinterpret_cast<double*>(base + bp.off_radius);
+    HIP_TRY(hipMemcpy(d_cams, o->cameras, (size_t)o->n_cameras * sizeof(moshii_camera), hipMemcpyHostToDevice));
+    if (N > 0) {
+        HIP_TRY(hipMemcpy(d_radius, o->point_radius, (size_t)N * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(base + bp.off_prgb, o->point_rgb, (size_t)N * 3, hipMemcpyHostToDevice));
+    }
+    const size_t npix = (size_t)F * H * W;
+    Staging st(flags, stream);
+    const T* d_verts = posed ? (const T*)nullptr : st.in(verts, (size_t)F * V * 3);
+    const T* d_pose = posed ? st.in(pose, (size_t)F * m->NP) : (const T*)nullptr;
+    const T* d_trans = posed ? st.in(trans, (size_t)F * 3) : (const T*)nullptr;
+    const T* d_shape = posed ? st.in(shape, (size_t)F * m->nshape) : (const T*)nullptr;
+    const T* d_points = N > 0 ? st.in(points, (size_t)F * N * 3) : (const T*)nullptr;
+    uint8_t* d_rgb = st.out(rgb, npix * 3);
+    int32_t* d_ids = st.out(ids, npix);
+    float* d_depth = st.out(depth, npix);
+    if (!st.ok()) return fail_mem(st, name);
+    m->vmscratch.used = true; m->vmscratch.last_stream = stream;
+    RenderArgs A;
+    memset(&A, 0, sizeof(A));
+    A.V = V; A.NF = m->n_faces; A.N = N; A.W = W; A.H = H; A.w16 = m->vn_w16;
+    A.tris = m->d_sd_tris;
+    A.rec = reinterpret_cast<const RenderVertex*>(base + bp.off_rec);
+    A.mrec = reinterpret_cast<const RenderMarker*>(base + bp.off_mrec);
+    A.prgb = reinterpret_cast<const unsigned char*>(base + bp.off_prgb);
+    for (int i = 0; i < 3; ++i) { A.body[i] = o->body_rgb[i]; A.bg[i] = o->bg_rgb[i]; }
+    A.ambient = o->ambient;
+    const char* which = "";
+    int lds = 0, threads = 0;
+    for (long long f0 = 0; f0 < F; f0 += bp.batch) {
+        const int nf = (int)std::min<long long>(bp.batch, F - f0);
+        const T* mesh = posed ? d_mesh : d_verts + (size_t)f0 * V * 3;
+        if (posed)
+            HIP_TRY(export_batch(m, nf, d_pose + (size_t)f0 * m->NP, d_trans + (size_t)f0 * 3,
+                                 d_shape ? d_shape + (size_t)f0 * m->nshape : (const T*)nullptr, d_mesh, stream));
+        HIP_TRY(moshii_launch_vertex_normals(stream, V, nf, sizeof(T) == 8, mesh, d_normals, m->d_vn_rows, m->d_vn_pairs, m->vn_w16, nullptr, nullptr, nullptr));
+        const size_t p0 = (size_t)f0 * H * W;
+        A.rgb = d_rgb ? d_rgb + p0 * 3 : nullptr;
+        A.ids = d_ids ? d_ids + p0 : nullptr;
+        A.depth = d_depth ? d_depth + p0 : nullptr;
+        const int stride = o->n_cameras == 1 ? 0 : 1;
+        HIP_TRY(moshii_launch_render(stream, nf, sizeof(T) == 8, mesh, d_normals, d_points ? d_points + (size_t)f0 * N * 3 : (const T*)nullptr, d_radius,
+                                     d_cams + (stride ? f0 : 0), stride, &A, &which, &lds, &threads));
+    }
+    note_launch(which, lds, threads);
+    HIP_TRY(st.finish());
+    return MOSHII_OK;
+}
+
 extern "C" {
+
+int moshii_render_f32(moshii_model_t m, int32_t F, const float* verts, int32_t N, const float* points, const moshii_render_opts* opts,
+                      uint8_t* rgb, int32_t* ids, float* depth, uint32_t flags, void* stream) {
+    return render_impl<float>(m, F, verts, nullptr, nullptr, nullptr, false, N, points, opts, rgb, ids, depth, flags, stream, "moshii_render_f32");
+}
+int moshii_render_f64(moshii_model_t m, int32_t F, const double* verts, int32_t N, const double* points, const moshii_render_opts* opts,
+                      uint8_t* rgb, int32_t* ids, float* depth, uint32_t flags, void* stream) {
+    return render_impl<double>(m, F, verts, nullptr, nullptr, nullptr, false, N, points, opts, rgb, ids, depth, flags, stream, "moshii_render_f64");
+}
+int moshii_render_posed_f32(moshii_model_t m, int32_t F, const float* pose, const float* trans, const float* shape, int32_t N, const float* points,
+                            const moshii_render_opts* opts, uint8_t* rgb, int32_t* ids, float* depth, uint32_t flags, void* stream) {
+    return render_impl<float>(m, F, nullptr, pose, trans, shape, true, N, points, opts, rgb, ids, depth, flags, stream, "moshii_render_posed_f32");
+}
+int moshii_render_posed_f64(moshii_model_t m, int32_t F, const double* pose, const double* trans, const double* shape, int32_t N, const double* points,
+                            const moshii_render_opts* opts, uint8_t* rgb, int32_t* ids, float* depth, uint32_t flags, void* stream) {
+    return render_impl<double>(m, F, nullptr, pose, trans, shape, true, N, points, opts, rgb, ids, depth, flags, stream, "moshii_render_posed_f64");
+}
 
 int moshii_lbs_forward_f64(moshii_model_t m, int32_t F, const double* pose, const double* trans, double* verts,
                            uint32_t flags, void* stream) {

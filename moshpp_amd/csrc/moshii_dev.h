@@ -268,3 +268,30 @@ struct Lbs32Model {
     float sxscale;         // power of two: the coefficients are multiplied by it, the directions divided
     long long featcap;     // bytes of featF (the extended layout needs more per frame tile)
 };
+
+// ---- shaded previews (moshii_render_*; kernels in lbs_forward.hip, the rules in include/moshii.h) ----
+// what k_render_project leaves per (frame, vertex) and per (frame, marker) for k_render_tiles
+struct RenderVertex {      // 32 bytes
+    int sx, sy;            // screen position on the 1/16-pixel grid
+    double z;              // camera-space depth
+    float n[3];            // camera-space vertex normal (R . n rounded to f32)
+    int ok;                // 0: behind znear, non-finite or beyond 2^24 -- every triangle that names the vertex is dropped
+};
+struct RenderMarker {      // 40 bytes
+    double uc, vc;         // the disc's centre, pixels
+    double rx, ry;         // its half axes fx r / zc, fy r / zc, pixels
+    float depth;           // zc - r, the depth of every covered pixel
+    int ok;                // 0: skipped (non-finite, zc - r <= znear, r <= 0)
+};
+struct RenderArgs {
+    int V, NF, N, W, H, w16;
+    const unsigned* tris;          // the handle's face table (moshii_model_set_faces)
+    const RenderVertex* rec;       // [nf][V]
+    const RenderMarker* mrec;      // [nf][N]
+    const unsigned char* prgb;     // [N][3]
+    unsigned char body[3], bg[3];
+    double ambient;
+    unsigned char* rgb;            // [nf][H][W][3] or null
+    int* ids;                      // [nf][H][W] or null
+    float* depth;                  // [nf][H][W] or null
+};

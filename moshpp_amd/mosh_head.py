@@ -597,3 +597,94 @@ def stageii_joints(stageii_data_or_fname, surface_model=None, frame_ids=None, dt
     if out_fname is not None:
         np.savez(_makepath(str(out_fname)), **out)
     return out
+
+
+PREVIEW_BATCH = 32                # frames rendered per call: bounds the host memory a long sequence needs beside the images themselves
+
+
+def _stageii_preview_plan(pkl, surface_model, frame_ids, out_dir, size, contact_sheet_columns):
+    """Every refusal of stageii_preview that needs no model file and no device; (plan, observed[T, M, 3], simulated[T, M, 3] or None,
+    file names, contact-sheet file name or None)."""
+    plan = _stageii_vertices_plan(pkl, frame_ids)
+    ids = plan[5]
+    try:
+        W, H = (int(x) for x in size)
+    except (TypeError, ValueError):
+        raise ValueError(f'stageii_preview: size must be (width, height), got {size!r}') from None
+    if not (1 <= W <= 4096 and 1 <= H <= 4096):
+        raise ValueError(f'stageii_preview: width and height must be within 1 .. 4096, got {W} x {H}')
+    if contact_sheet_columns is not None and int(contact_sheet_columns) < 1:
+        raise ValueError(f'stageii_preview: contact_sheet_columns must be >= 1, got {contact_sheet_columns!r}')
+    if len(ids) == 0:
+        raise ValueError('stageii_preview: no frame to render')
+    if surface_model is not None and getattr(surface_model, 'f', None) is None:
+        raise ValueError('stageii_preview: the surface model has no faces (f)')
+    dbg = pkl['stageii_debug_details']
+    src = dbg if 'markers_obs' in dbg else pkl
+    T = np.asarray(pkl['fullpose']).shape[0]
+    obs, sim = np.zeros((len(ids), 0, 3)), None
+    if 'markers_obs' in src and 'labels_obs' in src:
+        if len(src['markers_obs']) != T or len(src['labels_obs']) != T:
+            raise ValueError(f"stageii_preview: markers_obs / labels_obs hold {len(src['markers_obs'])} / {len(src['labels_obs'])} frames, "
+                             f"the result {T}")
+        labels = list(pkl['latent_labels']) if 'latent_labels' in pkl else list(dict.fromkeys(l for row in src['labels_obs'] for l in row))
+        from .chmosh import pack_observed_markers
+        try:
+            obs = pack_observed_markers(src['markers_obs'], src['labels_obs'], labels, ids)
+            if 'markers_sim' in src:
+                sim = pack_observed_markers(src['markers_sim'], src['labels_obs'], labels, ids)
+        except ValueError as e:
+            raise ValueError(f'stageii_preview: {e}') from None
+    fnames, sheet = [], None
+    if out_dir is not None:
+        fnames = [osp.join(str(out_dir), 'frame_%06d.png' % int(f)) for f in ids]
+        if len(set(fnames)) != len(fnames):
+            raise ValueError('stageii_preview: frame_ids names a frame twice, its file would be written twice')
+        if contact_sheet_columns is not None:
+            sheet = osp.join(str(out_dir), 'contact_sheet.png')
+        for fn in fnames + ([sheet] if sheet else []):
+            if osp.exists(fn):
+                raise FileExistsError(f'stageii_preview: {fn} exists; remove it or choose another directory')
+    return plan, obs, sim, fnames, sheet
+
+
+def stageii_preview(stageii_data_or_fname, out_dir=None, surface_model=None, frame_ids=None, size=(512, 512), view='front',
+                    contact_sheet_columns=None, up='z', marker_radius=0.0095):
+    """Pictures of a Stage-II result (pickle file name or dict), what the reference shows while it solves (tools/visualization.py:96-130):
+    the solved body of every frame with the observed markers (red) and, where the result stores them, the solve's simulated markers
+    (blue), rasterised on the device by the rendering rules of include/moshii.h; the meshes never reach the host.
+
+    One camera for the whole sequence (preview.preview_camera of the frames' posed joints, from `view` with the world axis `up` upwards).
+    out_dir: receives frame_%06d.png (the number is the row of the result) and, with contact_sheet_columns, contact_sheet.png; it is
+    created; an existing file is refused before any work.  Frames are rendered PREVIEW_BATCH at a time.
+    Returns dict(images[T, H, W, 3] uint8, camera, frame_ids, fnames, contact_sheet (the image, or None), contact_sheet_fname).
+    surface_model / frame_ids: as in stageii_vertices."""
+    from . import preview, png_io
+    pkl = _stageii_load(stageii_data_or_fname)
+    plan, obs, sim, fnames, sheet_fname = _stageii_preview_plan(pkl, surface_model, frame_ids, out_dir, size, contact_sheet_columns)
+    sm, mp, kind, start, count, ids = plan
+    surface_model, shapedirs, b, fullpose, trans, coef = _stageii_export_inputs(pkl, plan, surface_model)
+    if getattr(surface_model, 'f', None) is None:
+        raise ValueError('stageii_preview: the surface model has no faces (f)')
+    points = obs if sim is None else np.concatenate([obs, sim], axis=1)
+    N = points.shape[1]
+    prgb = np.array([preview.OBSERVED_RGB] * obs.shape[1] + [preview.SIMULATED_RGB] * (N - obs.shape[1]), dtype=np.uint8).reshape(N, 3)
+    W, H = int(size[0]), int(size[1])
+    images = np.zeros((len(ids), H, W, 3), dtype=np.uint8)
+    dev = _stageii_device(surface_model, shapedirs, b, kind, start, count)
+    try:
+        dev.set_faces(surface_model.f)
+        camera = preview.preview_camera(dev.posed_joints(fullpose, trans, shape=coef), (W, H), view=view, up=up)
+        for a in range(0, len(ids), PREVIEW_BATCH):
+            z = slice(a, a + PREVIEW_BATCH)
+            images[z] = dev.render_posed(fullpose[z], trans[z], camera, (W, H), points=points[z] if N else None, point_rgb=prgb if N else None,
+                                         point_radius=float(marker_radius) if N else None, shape=None if coef is None else coef[z],
+                                         outputs=('rgb',))['rgb']
+    finally:
+        dev.close()
+    sheet = preview.contact_sheet(images, contact_sheet_columns) if contact_sheet_columns is not None else None
+    for fn, img in zip(fnames, images):
+        png_io.write_png(_makepath(fn), img)
+    if sheet_fname is not None:
+        png_io.write_png(_makepath(sheet_fname), sheet)
+    return dict(images=images, camera=camera, frame_ids=np.asarray(ids), fnames=fnames, contact_sheet=sheet, contact_sheet_fname=sheet_fname)

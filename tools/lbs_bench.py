@@ -12,7 +12,11 @@ kernel, the gather kernel in f32 and f64, and the fused entry (export + distance
 tests per second and the share of the f32 vector peak the tests' arithmetic comes to.
 --joints [F] [--model NAME]: posed joints and world joint rotations (moshii_joints_*) of F frames (default 4000, smplh) on device
 buffers, f32 and f64, with and without the rotations: HIP events around one call, median of 20 after 3 warm-ups, the launch shape and
-the bytes moved; beside it moshii_lbs_forward_f32 on the same frames, timed the same way."""
+the bytes moved; beside it moshii_lbs_forward_f32 on the same frames, timed the same way.
+--render [F] [--size W] [--model NAME]: shaded previews (moshii_render_f32) of F frames (default 256, smplh) at W x W (default 512) with
+53 + 53 markers on device buffers, one fitted camera: HIP events around one call, median of 10 after 3 warm-ups -- the export alone, the
+normals alone, the render call (normals + k_render_project + k_render_tiles) and, as the difference of the last two, project + tiles;
+ms per frame each, and the fused moshii_render_posed_f32 for the whole chain."""
 import ctypes as C, sys, time
 import numpy as np
 sys.path.insert(0, '.')
@@ -252,6 +256,100 @@ def joints_bench(argv):
           f'f32 vs f64 joints on all frames: max |diff| {np.abs(keep[np.float32][2] - keep[np.float64][2]).max():.1e} m')
 
 
+def render_bench(argv):
+    import os
+    import torch
+    from moshpp_amd import preview, synth, workload
+    mt, W = 'smplh', 512
+    for flag in ('--model', '--size'):
+        if flag in argv:
+            i = argv.index(flag)
+            if flag == '--model':
+                mt = argv[i + 1]
+            else:
+                W = int(argv[i + 1])
+            del argv[i:i + 2]
+    F = int(argv[0]) if len(argv) > 0 else 256
+    M = {'smplh': 53, 'smpl': 41, 'smplx': 89, 'mano': 33}[mt]
+    dd = synth.synth_mesh_model(mt, seed=1000)
+    job = workload.make_job(mt, 8, M, seed=1000, optimize_fingers=(mt == 'mano'), dd=dd)
+    solver = workload.make_solver(job)
+    model, sm = solver.dev, job['sm']
+    faces = np.asarray(dd['f'], dtype=np.int32)
+    model.set_faces(faces)
+    V, NF, N = sm.V, len(faces), 2 * 53
+    dev = torch.device('cuda', 0)
+    rng = np.random.default_rng(0)
+    pose_h = rng.normal(0, 0.3, (F, sm.NP)).astype(np.float32)
+    trans_h = rng.normal(0, 0.1, (F, 3)).astype(np.float32)
+    cam = preview.preview_camera(model.posed_joints(pose_h, trans_h, dtype=np.float32), (W, W), view=(20.0, 10.0), up='y')
+    vids = rng.choice(V, 53, replace=False)
+    pts_h = np.zeros((F, N, 3), dtype=np.float32)
+    pose, trans = torch.from_numpy(pose_h).to(dev), torch.from_numpy(trans_h).to(dev)
+    verts = torch.empty((F, V, 3), dtype=torch.float32, device=dev)
+    normals = torch.empty((F, V, 3), dtype=torch.float32, device=dev)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    export = lambda: model.lbs_forward_device(F, pose.data_ptr(), trans.data_ptr(), verts.data_ptr(), stream)
+    nrm = lambda: model.vertex_normals_device(F, verts.data_ptr(), normals.data_ptr(), stream)
+    export(); nrm()
+    torch.cuda.synchronize()
+    vh, nh = verts[:, vids].cpu().numpy(), normals[:, vids].cpu().numpy()
+    pts_h[:, :53] = vh + 0.0095 * nh                       # markers where a solve would put them: on the skin, 9.5 mm out
+    pts_h[:, 53:] = vh + 0.0095 * nh + rng.normal(0, 0.004, vh.shape).astype(np.float32)
+    pts = torch.from_numpy(pts_h).to(dev)
+    prgb = np.array([preview.OBSERVED_RGB] * 53 + [preview.SIMULATED_RGB] * 53, dtype=np.uint8)
+    rgb = torch.empty((F, W, W, 3), dtype=torch.uint8, device=dev)
+    ids = torch.empty((F, W, W), dtype=torch.int32, device=dev)
+    depth = torch.empty((F, W, W), dtype=torch.float32, device=dev)
+    kw = dict(N=N, points_ptr=pts.data_ptr(), point_rgb=prgb, point_radius=0.0095, rgb_ptr=rgb.data_ptr(), ids_ptr=ids.data_ptr(),
+              depth_ptr=depth.data_ptr(), stream=stream)
+    render = lambda: model.render_device(F, verts.data_ptr(), cam, (W, W), **kw)
+    fused = lambda: model.render_posed_device(F, pose.data_ptr(), trans.data_ptr(), cam, (W, W), **kw)
+
+    def timed(fn):                      # HIP events around ONE call, median of 10 after 3 warm-ups
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(10):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return np.median(ts), min(ts), max(ts)
+
+    print(f'{mt} mesh body: V = {V}, {NF} faces, {N} markers, F = {F} frames at {W} x {W}, one camera, rgb + ids + depth, device buffers, HIP events '
+          f'around one call, median of 10 calls after 3 warm-ups (fastest .. slowest); library {os.path.basename(capi.LIB_PATH)} '
+          f'{capi.load().moshii_source_hash().decode()}')
+    res = {}
+    for name, fn in (('export (moshii_lbs_forward_f32)', export), ('normals (moshii_vertex_normals_f32)', nrm),
+                     ('render call: normals + project + tiles', render), ('fused: export + normals + project + tiles', fused)):
+        med, lo, hi = timed(fn)
+        res[name] = med
+        print(f'  {name:44s} {med:9.3f} ms ({lo:.3f} .. {hi:.3f})   {med / F * 1e3:9.2f} us a frame')
+    kname, klds, kthreads = capi.last_launch_info()
+    tiles = ((W + 31) // 32) ** 2
+    pt = res['render call: normals + project + tiles'] - res['normals (moshii_vertex_normals_f32)']
+    feed = res['export (moshii_lbs_forward_f32)'] + res['normals (moshii_vertex_normals_f32)']
+    print(f'  ({kname}: {tiles} tiles x {F} frames = {tiles * F} workgroups of {kthreads} threads, {klds} B of LDS each; {(NF + N + 1023) // 1024} list chunks a tile)')
+    print(f'  project + tiles (render call - normals)      {pt:9.3f} ms   {pt / F:9.4f} ms a frame')
+    print(f'  export + normals that feed them              {feed:9.3f} ms   {feed / F:9.4f} ms a frame')
+    print(f'  the rasteriser costs {pt / feed:.1f} x the export and normals it consumes')
+    torch.cuda.synchronize()
+    host = model.render(verts[:2].cpu().numpy(), cam, (W, W), points=pts_h[:2], point_rgb=prgb, point_radius=0.0095)
+    same = all(np.array_equal(host[k], a[:2].cpu().numpy()) for k, a in (('rgb', rgb), ('ids', ids), ('depth', depth)))
+    i0 = ids[0].cpu().numpy()
+    print(f'  check: device-buffer call vs the host-buffer call on 2 frames: {"same bits" if same else "DIFFERENT"}; frame 0: background '
+          f'{100 * (i0 < 0).mean():.1f} %, body {100 * ((i0 >= 0) & (i0 < NF)).mean():.1f} %, markers {100 * (i0 >= NF).mean():.2f} %')
+
+
+if '--render' in sys.argv:
+    from moshpp_amd import capi
+    sys.argv.remove('--render')
+    render_bench(sys.argv[1:])
+    sys.exit(0)
 if '--joints' in sys.argv:
     from moshpp_amd import capi
     sys.argv.remove('--joints')

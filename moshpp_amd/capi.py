@@ -97,10 +97,17 @@ class RenderOpts(C.Structure):
                 ('point_radius', _c_double_p)]
 
 
-_RENDER_ARGS = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(RenderOpts), C.c_void_p, C.c_void_p, C.c_void_p,
-                C.c_uint32, C.c_void_p]
-_RENDER_POSED_ARGS = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(RenderOpts), C.c_void_p,
-                      C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+_P, _I, _U = C.c_void_p, C.c_int32, C.c_uint32
+# one argtypes list per f32 / f64 pair of entries: the two differ in what the buffers hold, not in their arguments
+_LBS_ARGS = [_P, _I, _P, _P, _P, _U, _P]
+_LBS_SHAPE_ARGS = [_P, _I, _P, _P, _P, _P, _U, _P]
+_NORMALS_ARGS = [_P, _I, _P, _P, _U, _P]
+_VMARKERS_ARGS = [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _U, _P]
+_SDIST_ARGS = [_P, _I, _P, _I, _P, _P, _P, _P, _P, _U, _P]
+_MSDIST_ARGS = [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _U, _P]
+_JOINTS_ARGS = [_P, _I, _P, _P, _P, _P, _P, _U, _P]
+_RENDER_ARGS = [_P, _I, _P, _I, _P, C.POINTER(RenderOpts), _P, _P, _P, _U, _P]
+_RENDER_POSED_ARGS = [_P, _I, _P, _P, _P, _I, _P, C.POINTER(RenderOpts), _P, _P, _P, _U, _P]
 
 EXPORTS = {
     # name: (restype, argtypes)
@@ -115,27 +122,21 @@ EXPORTS = {
     'moshii_model_set_betas': (C.c_int, [C.c_void_p, _c_double_p, C.c_int32]),
     'moshii_model_set_free_shape': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     'moshii_model_get_joints': (C.c_int, [C.c_void_p, _c_double_p]),
-    'moshii_lbs_forward_f64': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    'moshii_lbs_forward_f32': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    'moshii_lbs_forward_shape_f64': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    'moshii_lbs_forward_shape_f32': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    'moshii_lbs_forward_f64': (C.c_int, _LBS_ARGS),
+    'moshii_lbs_forward_f32': (C.c_int, _LBS_ARGS),
+    'moshii_lbs_forward_shape_f64': (C.c_int, _LBS_SHAPE_ARGS),
+    'moshii_lbs_forward_shape_f32': (C.c_int, _LBS_SHAPE_ARGS),
     'moshii_model_set_faces': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
-    'moshii_vertex_normals_f32': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    'moshii_vertex_normals_f64': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    'moshii_virtual_markers_f32': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    'moshii_virtual_markers_f64': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    'moshii_surface_distance_f32': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.c_uint32, C.c_void_p]),
-    'moshii_surface_distance_f64': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.c_uint32, C.c_void_p]),
-    'moshii_marker_surface_distance_f32': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
-                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    'moshii_marker_surface_distance_f64': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
-                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    'moshii_joints_f32': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    'moshii_joints_f64': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    'moshii_vertex_normals_f32': (C.c_int, _NORMALS_ARGS),
+    'moshii_vertex_normals_f64': (C.c_int, _NORMALS_ARGS),
+    'moshii_virtual_markers_f32': (C.c_int, _VMARKERS_ARGS),
+    'moshii_virtual_markers_f64': (C.c_int, _VMARKERS_ARGS),
+    'moshii_surface_distance_f32': (C.c_int, _SDIST_ARGS),
+    'moshii_surface_distance_f64': (C.c_int, _SDIST_ARGS),
+    'moshii_marker_surface_distance_f32': (C.c_int, _MSDIST_ARGS),
+    'moshii_marker_surface_distance_f64': (C.c_int, _MSDIST_ARGS),
+    'moshii_joints_f32': (C.c_int, _JOINTS_ARGS),
+    'moshii_joints_f64': (C.c_int, _JOINTS_ARGS),
     'moshii_render_f32': (C.c_int, _RENDER_ARGS),
     'moshii_render_f64': (C.c_int, _RENDER_ARGS),
     'moshii_render_posed_f32': (C.c_int, _RENDER_POSED_ARGS),
@@ -208,6 +209,11 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _need_float(who, dtype):
+    if dtype not in (np.float64, np.float32):
+        raise ValueError(f'{who}: dtype must be numpy float64 or float32, not {dtype!r}')
+
+
 def _dp(a):
     return a.ctypes.data_as(_c_double_p)
 
@@ -216,8 +222,27 @@ def _ip(a):
     return a.ctypes.data_as(_c_int_p)
 
 
-class DeviceBuffer:
+class _Owner:
+    """Owner of one thing of the library's: close() gives it back once, __del__ does so quietly.  An object that never got as far as
+    holding it (a failed or skipped __init__) closes as nothing."""
+    _slot, _destroy, _closed = 'handle', None, C.c_void_p   # the attribute, the entry that frees it, what the attribute is afterwards
+
+    def close(self):
+        h = getattr(self, self._slot, None)
+        if h:
+            getattr(load(), self._destroy)(h)
+            setattr(self, self._slot, self._closed())
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceBuffer(_Owner):
     """A device allocation of the library's own (for callers that chain device-buffer calls without another allocator)."""
+    _slot, _destroy, _closed = 'ptr', 'moshii_internal_dev_free', type(None)
 
     def __init__(self, nbytes):
         lib = load()
@@ -238,17 +263,6 @@ class DeviceBuffer:
             raise MoshiiError('device -> host copy failed')
         return out
 
-    def close(self):
-        if getattr(self, 'ptr', None):
-            load().moshii_internal_dev_free(self.ptr)
-            self.ptr = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class SurfaceDistance:
     """What Model.surface_distance / marker_surface_distance return: distance[F, N] (signed, metres), face[F, N], part[F, N]
@@ -264,8 +278,9 @@ class SurfaceDistance:
                    np.zeros((F, N, 3), dtype=dtype))
 
 
-class Model:
+class Model(_Owner):
     """moshii_model_t: body model arrays + pose-variable layout, resident in HBM."""
+    _destroy = 'moshii_model_destroy'
 
     def __init__(self, v_template, shapedirs, posedirs, weights, J_regressor, parents, body_dof, hand_dof=0,
                  hands_mean=None, selected_components=None):
@@ -322,22 +337,44 @@ class Model:
         """verts[F,V,3] for pose variables pose[F,NP], trans[F,3] (host arrays).  shape[F, nshape]: per-frame coefficients of the
         block declared with set_free_shape (the `shape` a Stage-II solve returns: expression / DMPL offsets on the frozen betas);
         rest positions and joints follow them."""
-        if dtype not in (np.float64, np.float32):
-            raise ValueError(f'lbs_forward: dtype must be numpy float64 or float32, not {dtype!r}')
+        _need_float('lbs_forward', dtype)
+        pose, trans, shape, F = self._posed_inputs('lbs_forward', pose, trans, shape, dtype)
+        out = np.zeros((F, self.V, 3), dtype=dtype)
+        if shape is None:
+            fn = self._entry('lbs_forward', dtype == np.float32)
+            check(fn(self.handle, F, pose.ctypes.data, trans.ctypes.data, out.ctypes.data, BUFFERS_HOST, None))
+        else:
+            fn = self._entry('lbs_forward_shape', dtype == np.float32)
+            check(fn(self.handle, F, pose.ctypes.data, trans.ctypes.data, shape.ctypes.data, out.ctypes.data, BUFFERS_HOST, None))
+        return out
+
+    @staticmethod
+    def _entry(stem, f32):
+        """The library's moshii_<stem>_f32 or moshii_<stem>_f64."""
+        return getattr(load(), 'moshii_' + stem + ('_f32' if f32 else '_f64'))
+
+    def _posed_inputs(self, who, pose, trans, shape, dtype):
+        """(pose[F, NP], trans[F, 3], shape[F, nshape] | None, F) as contiguous arrays of `dtype` (checked by the caller, _need_float, ahead
+        of its own checks); ValueError, before any device call, if they cannot be that."""
         pose = np.ascontiguousarray(np.atleast_2d(pose), dtype=dtype)
         trans = np.ascontiguousarray(np.atleast_2d(trans), dtype=dtype)
         F = pose.shape[0]
-        assert pose.shape == (F, self.NP) and trans.shape == (F, 3)
+        if pose.shape != (F, self.NP) or trans.shape != (F, 3):
+            raise ValueError(f'{who}: pose / trans must be [F, {self.NP}] / [F, 3], got {pose.shape} / {trans.shape}')
         if shape is not None:
             shape = self._check_shape_rows(shape, F, dtype)
-        out = np.zeros((F, self.V, 3), dtype=dtype)
-        if shape is None:
-            fn = load().moshii_lbs_forward_f64 if dtype == np.float64 else load().moshii_lbs_forward_f32
-            check(fn(self.handle, F, pose.ctypes.data, trans.ctypes.data, out.ctypes.data, BUFFERS_HOST, None))
-        else:
-            fn = load().moshii_lbs_forward_shape_f64 if dtype == np.float64 else load().moshii_lbs_forward_shape_f32
-            check(fn(self.handle, F, pose.ctypes.data, trans.ctypes.data, shape.ctypes.data, out.ctypes.data, BUFFERS_HOST, None))
-        return out
+        return pose, trans, shape, F
+
+    def _mesh_inputs(self, who, verts, dtype=None):
+        """verts[F, V, 3] (a lone [V, 3] becomes [1, V, 3]) as a contiguous array of `dtype`; None: of its own dtype, which must then be
+        float32 or float64."""
+        verts = np.asarray(verts)
+        if dtype is None and verts.dtype not in (np.float32, np.float64):
+            raise ValueError(f'{who}: verts must be float32 or float64, not {verts.dtype}')
+        v = verts[None] if verts.ndim == 2 else verts
+        if v.ndim != 3 or v.shape[1:] != (self.V, 3):
+            raise ValueError(f'{who}: verts must be [F, {self.V}, 3], got {tuple(verts.shape)}')
+        return np.ascontiguousarray(v, dtype=dtype)
 
     def _check_shape_rows(self, shape, F, dtype):
         """shape[F, nshape] as a contiguous array of `dtype`; ValueError (before any device call) if it cannot be that."""
@@ -374,25 +411,23 @@ class Model:
         if int(getattr(self, 'n_faces', 0)) <= 0:
             raise ValueError(f'{who}: the model has no faces (set_faces)')
 
+    def _need_free_shape(self, who, shape_ptr):
+        if shape_ptr is not None and int(getattr(self, 'n_free_shape', 0)) <= 0:
+            raise ValueError(f'{who}: shape_ptr given, but the model has no free shape block (set_free_shape)')
+
     def vertex_normals(self, verts):
         """Area-weighted unit vertex normals [F, V, 3] of the meshes verts[F, V, 3] (or [V, 3]); float32 or float64 as the array."""
         self._need_faces('vertex_normals')
         verts = np.asarray(verts)
-        if verts.dtype not in (np.float32, np.float64):
-            raise ValueError(f'vertex_normals: verts must be float32 or float64, not {verts.dtype}')
-        one = verts.ndim == 2
-        v = verts[None] if one else verts
-        if v.ndim != 3 or v.shape[1:] != (self.V, 3):
-            raise ValueError(f'vertex_normals: verts must be [F, {self.V}, 3], got {tuple(verts.shape)}')
-        v = np.ascontiguousarray(v)
+        v = self._mesh_inputs('vertex_normals', verts)
         out = np.zeros_like(v)
-        fn = load().moshii_vertex_normals_f64 if v.dtype == np.float64 else load().moshii_vertex_normals_f32
+        fn = self._entry('vertex_normals', v.dtype == np.float32)
         check(fn(self.handle, v.shape[0], v.ctypes.data, out.ctypes.data, BUFFERS_HOST, None))
-        return out[0] if one else out
+        return out[0] if verts.ndim == 2 else out
 
     def vertex_normals_device(self, F, verts_ptr, normals_ptr, stream=None, f32=True):
         self._need_faces('vertex_normals_device')
-        fn = load().moshii_vertex_normals_f32 if f32 else load().moshii_vertex_normals_f64
+        fn = self._entry('vertex_normals', f32)
         check(fn(self.handle, F, verts_ptr, normals_ptr, BUFFERS_DEVICE, stream))
 
     def _check_markers(self, vids, dist, dtype, who):
@@ -411,21 +446,14 @@ class Model:
     def virtual_markers(self, pose, trans, vids, dist, dtype=np.float64, shape=None, return_normals=False):
         """markers[F, M, 3] = verts_f[vids] + dist * vertex normal, frame by frame, for pose variables pose[F, NP], trans[F, 3] (host
         arrays) -- the meshes never leave the device.  shape as in lbs_forward.  return_normals: (markers, normals[F, M, 3])."""
-        if dtype not in (np.float64, np.float32):
-            raise ValueError(f'virtual_markers: dtype must be numpy float64 or float32, not {dtype!r}')
+        _need_float('virtual_markers', dtype)
         self._need_faces('virtual_markers')
         vids, dist = self._check_markers(vids, dist, dtype, 'virtual_markers')
-        pose = np.ascontiguousarray(np.atleast_2d(pose), dtype=dtype)
-        trans = np.ascontiguousarray(np.atleast_2d(trans), dtype=dtype)
-        F = pose.shape[0]
-        if pose.shape != (F, self.NP) or trans.shape != (F, 3):
-            raise ValueError(f'virtual_markers: pose / trans must be [F, {self.NP}] / [F, 3], got {pose.shape} / {trans.shape}')
-        if shape is not None:
-            shape = self._check_shape_rows(shape, F, dtype)
+        pose, trans, shape, F = self._posed_inputs('virtual_markers', pose, trans, shape, dtype)
         M = len(vids)
         out = np.zeros((F, M, 3), dtype=dtype)
         nrm = np.zeros((F, M, 3), dtype=dtype) if return_normals else None
-        fn = load().moshii_virtual_markers_f64 if dtype == np.float64 else load().moshii_virtual_markers_f32
+        fn = self._entry('virtual_markers', dtype == np.float32)
         check(fn(self.handle, F, pose.ctypes.data, trans.ctypes.data, shape.ctypes.data if shape is not None else None, M,
                  vids.ctypes.data, dist.ctypes.data, out.ctypes.data, nrm.ctypes.data if return_normals else None, BUFFERS_HOST, None))
         return (out, nrm) if return_normals else out
@@ -434,7 +462,7 @@ class Model:
         """Device buffers for pose / trans / shape / markers / normals; vids and dist are host arrays."""
         self._need_faces('virtual_markers_device')
         vids, dist = self._check_markers(vids, dist, np.float32 if f32 else np.float64, 'virtual_markers_device')
-        fn = load().moshii_virtual_markers_f32 if f32 else load().moshii_virtual_markers_f64
+        fn = self._entry('virtual_markers', f32)
         check(fn(self.handle, F, pose_ptr, trans_ptr, shape_ptr, len(vids), vids.ctypes.data, dist.ctypes.data, out_ptr, normals_ptr,
                  BUFFERS_DEVICE, stream))
 
@@ -457,17 +485,13 @@ class Model:
         verts = np.asarray(verts)
         if dtype is None:
             dtype = np.float32 if verts.dtype == np.float32 else np.float64
-        if dtype not in (np.float64, np.float32):
-            raise ValueError(f'surface_distance: dtype must be numpy float64 or float32, not {dtype!r}')
+        _need_float('surface_distance', dtype)
         self._need_faces('surface_distance')
-        v = verts[None] if verts.ndim == 2 else verts
-        if v.ndim != 3 or v.shape[1:] != (self.V, 3):
-            raise ValueError(f'surface_distance: verts must be [F, {self.V}, 3], got {tuple(verts.shape)}')
-        v = np.ascontiguousarray(v, dtype=dtype)
+        v = self._mesh_inputs('surface_distance', verts, dtype)
         F = v.shape[0]
         points = self._check_points(points, F, dtype, 'surface_distance')
         res = SurfaceDistance.empty(F, points.shape[1], dtype)
-        fn = load().moshii_surface_distance_f64 if dtype == np.float64 else load().moshii_surface_distance_f32
+        fn = self._entry('surface_distance', dtype == np.float32)
         check(fn(self.handle, F, v.ctypes.data, points.shape[1], points.ctypes.data, res.distance.ctypes.data, res.face.ctypes.data,
                  res.part.ctypes.data, res.nearest.ctypes.data, BUFFERS_HOST, None))
         return res
@@ -476,25 +500,18 @@ class Model:
                                 f32=True):
         """Device buffers (f32: float, else double; face / part int32); asynchronous on `stream`."""
         self._need_faces('surface_distance_device')
-        fn = load().moshii_surface_distance_f32 if f32 else load().moshii_surface_distance_f64
+        fn = self._entry('surface_distance', f32)
         check(fn(self.handle, F, verts_ptr, N, points_ptr, dist_ptr, face_ptr, part_ptr, nearest_ptr, BUFFERS_DEVICE, stream))
 
     def marker_surface_distance(self, pose, trans, points, shape=None, dtype=np.float64):
         """surface_distance of points[F, N, 3] against the meshes of pose[F, NP], trans[F, 3] (shape as in lbs_forward) -- the meshes
         never leave the device."""
-        if dtype not in (np.float64, np.float32):
-            raise ValueError(f'marker_surface_distance: dtype must be numpy float64 or float32, not {dtype!r}')
+        _need_float('marker_surface_distance', dtype)
         self._need_faces('marker_surface_distance')
-        pose = np.ascontiguousarray(np.atleast_2d(pose), dtype=dtype)
-        trans = np.ascontiguousarray(np.atleast_2d(trans), dtype=dtype)
-        F = pose.shape[0]
-        if pose.shape != (F, self.NP) or trans.shape != (F, 3):
-            raise ValueError(f'marker_surface_distance: pose / trans must be [F, {self.NP}] / [F, 3], got {pose.shape} / {trans.shape}')
-        if shape is not None:
-            shape = self._check_shape_rows(shape, F, dtype)
+        pose, trans, shape, F = self._posed_inputs('marker_surface_distance', pose, trans, shape, dtype)
         points = self._check_points(points, F, dtype, 'marker_surface_distance')
         res = SurfaceDistance.empty(F, points.shape[1], dtype)
-        fn = load().moshii_marker_surface_distance_f64 if dtype == np.float64 else load().moshii_marker_surface_distance_f32
+        fn = self._entry('marker_surface_distance', dtype == np.float32)
         check(fn(self.handle, F, pose.ctypes.data, trans.ctypes.data, shape.ctypes.data if shape is not None else None, points.shape[1],
                  points.ctypes.data, res.distance.ctypes.data, res.face.ctypes.data, res.part.ctypes.data, res.nearest.ctypes.data,
                  BUFFERS_HOST, None))
@@ -504,9 +521,8 @@ class Model:
                                        stream=None, f32=True, shape_ptr=None):
         """Device buffers for pose / trans / shape / points and the results; asynchronous on `stream`."""
         self._need_faces('marker_surface_distance_device')
-        if shape_ptr is not None and int(getattr(self, 'n_free_shape', 0)) <= 0:
-            raise ValueError('marker_surface_distance_device: shape_ptr given, but the model has no free shape block (set_free_shape)')
-        fn = load().moshii_marker_surface_distance_f32 if f32 else load().moshii_marker_surface_distance_f64
+        self._need_free_shape('marker_surface_distance_device', shape_ptr)
+        fn = self._entry('marker_surface_distance', f32)
         check(fn(self.handle, F, pose_ptr, trans_ptr, shape_ptr, N, points_ptr, dist_ptr, face_ptr, part_ptr, nearest_ptr, BUFFERS_DEVICE, stream))
 
     # ---- the skeleton: posed joints and world joint rotations ----
@@ -515,18 +531,11 @@ class Model:
         arrays) -- forward kinematics alone, the reference's J_transformed.  shape as in lbs_forward (the joints move with the
         coefficients).  return_rotations: (joints, rot[F, K, 3, 3]), the world rotation of every joint (A_global's rotation part).
         float32 computes in float64 and rounds once.  joints() stays the REST joints."""
-        if dtype not in (np.float64, np.float32):
-            raise ValueError(f'posed_joints: dtype must be numpy float64 or float32, not {dtype!r}')
-        pose = np.ascontiguousarray(np.atleast_2d(pose), dtype=dtype)
-        trans = np.ascontiguousarray(np.atleast_2d(trans), dtype=dtype)
-        F = pose.shape[0]
-        if pose.shape != (F, self.NP) or trans.shape != (F, 3):
-            raise ValueError(f'posed_joints: pose / trans must be [F, {self.NP}] / [F, 3], got {pose.shape} / {trans.shape}')
-        if shape is not None:
-            shape = self._check_shape_rows(shape, F, dtype)
+        _need_float('posed_joints', dtype)
+        pose, trans, shape, F = self._posed_inputs('posed_joints', pose, trans, shape, dtype)
         out = np.zeros((F, self.K, 3), dtype=dtype)
         rot = np.zeros((F, self.K, 3, 3), dtype=dtype) if return_rotations else None
-        fn = load().moshii_joints_f64 if dtype == np.float64 else load().moshii_joints_f32
+        fn = self._entry('joints', dtype == np.float32)
         check(fn(self.handle, F, pose.ctypes.data, trans.ctypes.data, shape.ctypes.data if shape is not None else None, out.ctypes.data,
                  rot.ctypes.data if return_rotations else None, BUFFERS_HOST, None))
         return (out, rot) if return_rotations else out
@@ -534,9 +543,8 @@ class Model:
     def posed_joints_device(self, F, pose_ptr, trans_ptr, out_ptr, rot_ptr=None, stream=None, f32=True, shape_ptr=None):
         """Device buffers (f32: float, else double) for pose / trans / shape / joints[F][K][3] / rot[F][K][3][3]; asynchronous on
         `stream`."""
-        if shape_ptr is not None and int(getattr(self, 'n_free_shape', 0)) <= 0:
-            raise ValueError('posed_joints_device: shape_ptr given, but the model has no free shape block (set_free_shape)')
-        fn = load().moshii_joints_f32 if f32 else load().moshii_joints_f64
+        self._need_free_shape('posed_joints_device', shape_ptr)
+        fn = self._entry('joints', f32)
         check(fn(self.handle, F, pose_ptr, trans_ptr, shape_ptr, out_ptr, rot_ptr, BUFFERS_DEVICE, stream))
 
     # ---- shaded previews ----
@@ -597,13 +605,7 @@ class Model:
         point_radius[N] (or one radius, metres) are drawn as shaded discs, a NaN point is skipped.  ids: face id, n_faces + k for point
         k, -1 for background (depth +inf)."""
         self._need_faces('render')
-        verts = np.asarray(verts)
-        if verts.dtype not in (np.float32, np.float64):
-            raise ValueError(f'render: verts must be float32 or float64, not {verts.dtype}')
-        v = verts[None] if verts.ndim == 2 else verts
-        if v.ndim != 3 or v.shape[1:] != (self.V, 3):
-            raise ValueError(f'render: verts must be [F, {self.V}, 3], got {tuple(verts.shape)}')
-        v = np.ascontiguousarray(v)
+        v = self._mesh_inputs('render', verts)
         F = v.shape[0]
         N = 0
         if points is not None:
@@ -611,7 +613,7 @@ class Model:
             N = points.shape[1]
         o, keep = self._render_opts('render', F, cameras, size, N, point_rgb, point_radius, body_rgb, bg_rgb, ambient)
         res = self._render_outputs(F, o.width, o.height, outputs)
-        fn = load().moshii_render_f64 if v.dtype == np.float64 else load().moshii_render_f32
+        fn = self._entry('render', v.dtype == np.float32)
         check(fn(self.handle, F, v.ctypes.data, N, points.ctypes.data if N else None, C.byref(o),
                  *(res[k].ctypes.data if k in res else None for k in ('rgb', 'ids', 'depth')), BUFFERS_HOST, None))
         del keep
@@ -620,23 +622,16 @@ class Model:
     def render_posed(self, pose, trans, cameras, size, points=None, point_rgb=None, point_radius=None, shape=None, dtype=np.float32,
                      body_rgb=(200, 170, 150), bg_rgb=(255, 255, 255), ambient=0.3, outputs=('rgb', 'ids', 'depth')):
         """render() of the meshes of pose[F, NP], trans[F, 3] (shape as in lbs_forward) -- the meshes never leave the device."""
-        if dtype not in (np.float64, np.float32):
-            raise ValueError(f'render_posed: dtype must be numpy float64 or float32, not {dtype!r}')
+        _need_float('render_posed', dtype)
         self._need_faces('render_posed')
-        pose = np.ascontiguousarray(np.atleast_2d(pose), dtype=dtype)
-        trans = np.ascontiguousarray(np.atleast_2d(trans), dtype=dtype)
-        F = pose.shape[0]
-        if pose.shape != (F, self.NP) or trans.shape != (F, 3):
-            raise ValueError(f'render_posed: pose / trans must be [F, {self.NP}] / [F, 3], got {pose.shape} / {trans.shape}')
-        if shape is not None:
-            shape = self._check_shape_rows(shape, F, dtype)
+        pose, trans, shape, F = self._posed_inputs('render_posed', pose, trans, shape, dtype)
         N = 0
         if points is not None:
             points = self._check_points(points, F, dtype, 'render_posed')
             N = points.shape[1]
         o, keep = self._render_opts('render_posed', F, cameras, size, N, point_rgb, point_radius, body_rgb, bg_rgb, ambient)
         res = self._render_outputs(F, o.width, o.height, outputs)
-        fn = load().moshii_render_posed_f64 if dtype == np.float64 else load().moshii_render_posed_f32
+        fn = self._entry('render_posed', dtype == np.float32)
         check(fn(self.handle, F, pose.ctypes.data, trans.ctypes.data, shape.ctypes.data if shape is not None else None, N,
                  points.ctypes.data if N else None, C.byref(o), *(res[k].ctypes.data if k in res else None for k in ('rgb', 'ids', 'depth')),
                  BUFFERS_HOST, None))
@@ -648,7 +643,7 @@ class Model:
         """Device buffers for verts / points / rgb / ids / depth; cameras, colours and radii are host data; asynchronous on `stream`."""
         self._need_faces('render_device')
         o, keep = self._render_opts('render_device', F, cameras, size, N, point_rgb, point_radius, body_rgb, bg_rgb, ambient)
-        fn = load().moshii_render_f32 if f32 else load().moshii_render_f64
+        fn = self._entry('render', f32)
         check(fn(self.handle, F, verts_ptr, N, points_ptr, C.byref(o), rgb_ptr, ids_ptr, depth_ptr, BUFFERS_DEVICE, stream))
         del keep
 
@@ -657,26 +652,18 @@ class Model:
                             shape_ptr=None):
         """Device buffers for pose / trans / shape / points and the outputs; asynchronous on `stream`."""
         self._need_faces('render_posed_device')
-        if shape_ptr is not None and int(getattr(self, 'n_free_shape', 0)) <= 0:
-            raise ValueError('render_posed_device: shape_ptr given, but the model has no free shape block (set_free_shape)')
+        self._need_free_shape('render_posed_device', shape_ptr)
         o, keep = self._render_opts('render_posed_device', F, cameras, size, N, point_rgb, point_radius, body_rgb, bg_rgb, ambient)
-        fn = load().moshii_render_posed_f32 if f32 else load().moshii_render_posed_f64
+        fn = self._entry('render_posed', f32)
         check(fn(self.handle, F, pose_ptr, trans_ptr, shape_ptr, N, points_ptr, C.byref(o), rgb_ptr, ids_ptr, depth_ptr, BUFFERS_DEVICE, stream))
         del keep
 
     def lbs_forward_with_normals(self, pose, trans, dtype=np.float32, shape=None):
         """(verts, normals), both [F, V, 3]: the export into a device buffer, the normals from that buffer, two copies back -- the
         vertices do not visit the host in between."""
-        if dtype not in (np.float64, np.float32):
-            raise ValueError(f'lbs_forward_with_normals: dtype must be numpy float64 or float32, not {dtype!r}')
+        _need_float('lbs_forward_with_normals', dtype)
         self._need_faces('lbs_forward_with_normals')
-        pose = np.ascontiguousarray(np.atleast_2d(pose), dtype=dtype)
-        trans = np.ascontiguousarray(np.atleast_2d(trans), dtype=dtype)
-        F = pose.shape[0]
-        if pose.shape != (F, self.NP) or trans.shape != (F, 3):
-            raise ValueError(f'lbs_forward_with_normals: pose / trans must be [F, {self.NP}] / [F, 3], got {pose.shape} / {trans.shape}')
-        if shape is not None:
-            shape = self._check_shape_rows(shape, F, dtype)
+        pose, trans, shape, F = self._posed_inputs('lbs_forward_with_normals', pose, trans, shape, dtype)
         verts = np.zeros((F, self.V, 3), dtype=dtype)
         normals = np.zeros_like(verts)
         if F == 0:
@@ -698,28 +685,18 @@ class Model:
     def lbs_forward_device(self, F, pose_ptr, trans_ptr, out_ptr, stream=None, f32=True, shape_ptr=None):
         """Device buffers (f32: float, else double).  shape_ptr: [F][nshape] coefficients of the free shape block on the device."""
         if shape_ptr is None:
-            fn = load().moshii_lbs_forward_f32 if f32 else load().moshii_lbs_forward_f64
+            fn = self._entry('lbs_forward', f32)
             check(fn(self.handle, F, pose_ptr, trans_ptr, out_ptr, BUFFERS_DEVICE, stream))
         else:
-            if int(getattr(self, 'n_free_shape', 0)) <= 0:
-                raise ValueError('lbs_forward_device: shape_ptr given, but the model has no free shape block (set_free_shape)')
-            fn = load().moshii_lbs_forward_shape_f32 if f32 else load().moshii_lbs_forward_shape_f64
+            self._need_free_shape('lbs_forward_device', shape_ptr)
+            fn = self._entry('lbs_forward_shape', f32)
             check(fn(self.handle, F, pose_ptr, trans_ptr, shape_ptr, out_ptr, BUFFERS_DEVICE, stream))
 
-    def close(self):
-        if getattr(self, 'handle', None) is not None and self.handle.value:
-            load().moshii_model_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
-class Prior:
+class Prior(_Owner):
     """moshii_prior_t: prepared max-mixture prior (means, chols of precisions, re-normalised weights)."""
+    _destroy = 'moshii_prior_destroy'
 
     def __init__(self, means, chols, weights):
         means = _f64(means); chols = _f64(chols); weights = _f64(np.ravel(weights))
@@ -729,20 +706,11 @@ class Prior:
         self.handle = C.c_void_p()
         check(load().moshii_prior_create(G, npose, _dp(means), _dp(chols), _dp(weights), C.byref(self.handle)))
 
-    def close(self):
-        if getattr(self, 'handle', None) is not None and self.handle.value:
-            load().moshii_prior_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
-class Attachment:
+class Attachment(_Owner):
     """moshii_attach_t: closest[M,3] vertex ids + coef[M,3] -> compact marker-vertex model slice."""
+    _destroy = 'moshii_attach_destroy'
 
     def __init__(self, model: Model, closest, coef):
         closest = np.ascontiguousarray(closest, dtype=np.int32)
@@ -761,16 +729,6 @@ class Attachment:
         check(load().moshii_attach_markers(self.handle, F, _dp(pose), _dp(trans), _dp(out)))
         return out
 
-    def close(self):
-        if getattr(self, 'handle', None) is not None and self.handle.value:
-            load().moshii_attach_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def make_opts(weights, step1_ids, step2_ids, body_ids, finger_ids, maxiter=100, e3_first=1e-3, e3=1e-2,

@@ -223,68 +223,74 @@ class StageIISolver:
             return out
         raise ValueError(f'unknown chain_mode {chain_mode}')
 
+    def _posed(self, out, who, faces=False):
+        """(pose, trans, shape | None) of a solve() result for the exports below; faces: the export needs the model's triangles (which
+        the handle takes up in _set_faces_once, behind the export's other refusals)."""
+        for k in ('pose', 'trans') + (('shape',) if self.n_shape else ()):
+            if k not in out:
+                raise KeyError(f"StageIISolver.{who}: the result has no '{k}'")
+        if faces and getattr(self.sm, 'f', None) is None:
+            raise ValueError(f'StageIISolver.{who}: the surface model has no faces (f)')
+        return out['pose'], out['trans'], out['shape'] if self.n_shape else None
+
+    def _set_faces_once(self):
+        if not getattr(self.dev, 'n_faces', 0):
+            self.dev.set_faces(self.sm.f)
+
+    @staticmethod
+    def _observations(out, obs, vis, labels, who, required, F):
+        """points[F, M, 3], NaN where a marker is not observed: obs[F, M, 3] (and vis[F, M]) as solve() took them, or the ragged per-frame
+        lists out['markers_obs'] / out['labels_obs'] laid out over `labels`.  With neither: a KeyError if `required`, else no points."""
+        if obs is not None:
+            points = np.array(obs, dtype=np.float64)
+            if vis is not None:
+                points[~np.asarray(vis, dtype=bool)] = np.nan
+        elif required or ('markers_obs' in out and 'labels_obs' in out):
+            for k in ('markers_obs', 'labels_obs'):
+                if k not in out:
+                    raise KeyError(f"StageIISolver.{who}: no obs given and the result has no '{k}'")
+            if labels is None:
+                raise ValueError(f'StageIISolver.{who}: the ragged markers_obs / labels_obs need the label order (labels)')
+            points = pack_observed_markers(out['markers_obs'], out['labels_obs'], labels)
+        else:
+            points = np.zeros((F, 0, 3))
+        if points.ndim != 3 or points.shape[0] != F or points.shape[2] != 3:
+            raise ValueError(f'StageIISolver.{who}: the observations are {points.shape}, the result has {F} frames')
+        return points
+
     def vertices(self, out, dtype=np.float32):
         """verts[F, V, 3] of a solve() result: the full mesh the solved frames describe, on the solver's own model handle.  With a free
         block (optimize_face / optimize_dynamics) the per-frame coefficients out['shape'] move rest positions and joints exactly as in
         the solve, so the mesh carries the markers_sim the solver returned.  float32: the batched export kernels, float64: the
         reference-precision kernel.  Rows of unsolved frames (status 1) hold whatever pose the chain carried there."""
-        for k in ('pose', 'trans') + (('shape',) if self.n_shape else ()):
-            if k not in out:
-                raise KeyError(f"StageIISolver.vertices: the result has no '{k}'")
-        return self.dev.lbs_forward(out['pose'], out['trans'], dtype=dtype, shape=out['shape'] if self.n_shape else None)
+        pose, trans, shape = self._posed(out, 'vertices')
+        return self.dev.lbs_forward(pose, trans, dtype=dtype, shape=shape)
 
     def joints(self, out, dtype=np.float64, return_rotations=False):
         """joints[F, K, 3] of a solve() result: the world position of every joint on every solved frame (translation included; the
         reference's J_transformed) -- on the solver's own model handle, hand PCA and, with a free block, the per-frame coefficients
         out['shape'] included, so the skeleton is the one the solve moved.  return_rotations: (joints, rot[F, K, 3, 3]), the world
         rotation of every joint.  Rows of unsolved frames (status 1) hold whatever pose the chain carried there."""
-        for k in ('pose', 'trans') + (('shape',) if self.n_shape else ()):
-            if k not in out:
-                raise KeyError(f"StageIISolver.joints: the result has no '{k}'")
-        return self.dev.posed_joints(out['pose'], out['trans'], shape=out['shape'] if self.n_shape else None, dtype=dtype,
-                                     return_rotations=return_rotations)
+        pose, trans, shape = self._posed(out, 'joints')
+        return self.dev.posed_joints(pose, trans, shape=shape, dtype=dtype, return_rotations=return_rotations)
 
     def virtual_markers(self, out, vids, dist, dtype=np.float32, return_normals=False):
         """markers[F, M, 3] of a solve() result: vertex vids[i] of every solved frame's mesh + dist[i] x its vertex normal (the
         reference's marker placement rule, chmosh.py:57-67, on every frame) -- on the solver's own handle, the meshes stay on the
         device.  The surface model needs its triangles `f`."""
-        for k in ('pose', 'trans') + (('shape',) if self.n_shape else ()):
-            if k not in out:
-                raise KeyError(f"StageIISolver.virtual_markers: the result has no '{k}'")
-        if getattr(self.sm, 'f', None) is None:
-            raise ValueError('StageIISolver.virtual_markers: the surface model has no faces (f)')
-        if not getattr(self.dev, 'n_faces', 0):
-            self.dev.set_faces(self.sm.f)
-        return self.dev.virtual_markers(out['pose'], out['trans'], vids, dist, dtype=dtype, shape=out['shape'] if self.n_shape else None,
-                                        return_normals=return_normals)
+        pose, trans, shape = self._posed(out, 'virtual_markers', faces=True)
+        self._set_faces_once()
+        return self.dev.virtual_markers(pose, trans, vids, dist, dtype=dtype, shape=shape, return_normals=return_normals)
 
     def marker_skin_distance(self, out, obs=None, vis=None, labels=None, dtype=np.float32):
         """capi.SurfaceDistance of the observed markers against the solved skin, frame by frame (the reference's
         PtsToMesh(signed=True), scan2mesh/mesh_distance_main.py:158-297): distance[F, M] signed, in metres, NaN where a marker is not
         observed -- on the solver's own handle, the meshes stay on the device.  The observations: obs[F, M, 3] (and vis[F, M]) as
         solve() took them, or the ragged per-frame lists out['markers_obs'] / out['labels_obs'] laid out over `labels`."""
-        for k in ('pose', 'trans') + (('shape',) if self.n_shape else ()):
-            if k not in out:
-                raise KeyError(f"StageIISolver.marker_skin_distance: the result has no '{k}'")
-        if getattr(self.sm, 'f', None) is None:
-            raise ValueError('StageIISolver.marker_skin_distance: the surface model has no faces (f)')
-        F = np.atleast_2d(out['pose']).shape[0]
-        if obs is None:
-            for k in ('markers_obs', 'labels_obs'):
-                if k not in out:
-                    raise KeyError(f"StageIISolver.marker_skin_distance: no obs given and the result has no '{k}'")
-            if labels is None:
-                raise ValueError('StageIISolver.marker_skin_distance: the ragged markers_obs / labels_obs need the label order (labels)')
-            points = pack_observed_markers(out['markers_obs'], out['labels_obs'], labels)
-        else:
-            points = np.array(obs, dtype=np.float64)
-            if vis is not None:
-                points[~np.asarray(vis, dtype=bool)] = np.nan
-        if points.ndim != 3 or points.shape[0] != F or points.shape[2] != 3:
-            raise ValueError(f'StageIISolver.marker_skin_distance: the observations are {points.shape}, the result has {F} frames')
-        if not getattr(self.dev, 'n_faces', 0):
-            self.dev.set_faces(self.sm.f)
-        return self.dev.marker_surface_distance(out['pose'], out['trans'], points, shape=out['shape'] if self.n_shape else None, dtype=dtype)
+        pose, trans, shape = self._posed(out, 'marker_skin_distance', faces=True)
+        points = self._observations(out, obs, vis, labels, 'marker_skin_distance', True, np.atleast_2d(pose).shape[0])
+        self._set_faces_once()
+        return self.dev.marker_surface_distance(pose, trans, points, shape=shape, dtype=dtype)
 
     def render(self, out, obs=None, vis=None, camera=None, size=(512, 512), view='front', frame_ids=None, marker_radius=0.0095, labels=None,
                up='z', dtype=np.float32):
@@ -298,25 +304,10 @@ class StageIISolver:
         capi.Camera; default preview.preview_camera of the rendered frames' joints from `view` with the world axis `up` upwards.
         size = (width, height); frame_ids: rows of the result (default: all)."""
         from . import preview
-        for k in ('pose', 'trans') + (('shape',) if self.n_shape else ()):
-            if k not in out:
-                raise KeyError(f"StageIISolver.render: the result has no '{k}'")
-        if getattr(self.sm, 'f', None) is None:
-            raise ValueError('StageIISolver.render: the surface model has no faces (f)')
-        pose, trans = np.atleast_2d(out['pose']), np.atleast_2d(out['trans'])
+        pose, trans, shape = self._posed(out, 'render', faces=True)
+        pose, trans = np.atleast_2d(pose), np.atleast_2d(trans)
         F = pose.shape[0]
-        if obs is not None:
-            points = np.array(obs, dtype=np.float64)
-            if vis is not None:
-                points[~np.asarray(vis, dtype=bool)] = np.nan
-        elif 'markers_obs' in out and 'labels_obs' in out:
-            if labels is None:
-                raise ValueError('StageIISolver.render: the ragged markers_obs / labels_obs need the label order (labels)')
-            points = pack_observed_markers(out['markers_obs'], out['labels_obs'], labels)
-        else:
-            points = np.zeros((F, 0, 3))
-        if points.ndim != 3 or points.shape[0] != F or points.shape[2] != 3:
-            raise ValueError(f'StageIISolver.render: the observations are {points.shape}, the result has {F} frames')
+        points = self._observations(out, obs, vis, labels, 'render', False, F)
         n_obs = points.shape[1]
         sim = np.asarray(out['markers_sim'], dtype=np.float64) if 'markers_sim' in out else np.zeros((F, 0, 3))
         if sim.ndim != 3 or sim.shape[0] != F or sim.shape[2] != 3:
@@ -328,13 +319,12 @@ class StageIISolver:
             raise IndexError(f'StageIISolver.render: frame_ids outside the {F} solved frames')
         if not float(marker_radius) > 0.0:
             raise ValueError(f'StageIISolver.render: marker_radius must be positive, got {marker_radius!r}')
-        shape = np.atleast_2d(out['shape'])[ids] if self.n_shape else None
+        shape = np.atleast_2d(shape)[ids] if self.n_shape else None
         if camera is None:
             if len(ids) == 0:
                 raise ValueError('StageIISolver.render: no frame to frame a camera on; pass a camera')
             camera = preview.preview_camera(self.dev.posed_joints(pose[ids], trans[ids], shape=shape), size, view=view, up=up)
-        if not getattr(self.dev, 'n_faces', 0):
-            self.dev.set_faces(self.sm.f)
+        self._set_faces_once()
         allp = np.concatenate([points, sim], axis=1)[ids]
         N = allp.shape[1]
         prgb = np.array([preview.OBSERVED_RGB] * n_obs + [preview.SIMULATED_RGB] * (N - n_obs), dtype=np.uint8).reshape(N, 3)

@@ -17,6 +17,8 @@ import os
 import os.path as osp
 import pickle
 import time
+from collections import namedtuple
+from contextlib import contextmanager
 from datetime import timedelta
 
 import numpy as np
@@ -280,9 +282,13 @@ def load_as_amass_npz(stageii_pkl_data_or_fname, stageii_npz_fname=None, stagei_
     return out
 
 
+# what an export decides from the Stage-II dict alone: cfg.surface_model, cfg.moshpp, kind 'expr' | 'dmpl' | None of the free block, its
+# first column and size, the rows of the result to export
+_StageIIPlan = namedtuple('_StageIIPlan', 'sm mp kind start count ids')
+
+
 def _stageii_vertices_plan(pkl, frame_ids):
-    """Everything stageii_vertices decides from the Stage-II dict alone, checked before a model is loaded or a device touched:
-    (cfg.surface_model, kind 'expr' | 'dmpl' | None, block start, block size, frame ids)."""
+    """The _StageIIPlan of stageii_vertices (and of every other export), checked before a model is loaded or a device touched."""
     for k in ('fullpose', 'trans', 'betas', 'stageii_debug_details'):
         if k not in pkl:
             raise KeyError(f"stageii_vertices: the Stage-II data has no '{k}'")
@@ -322,7 +328,7 @@ def _stageii_vertices_plan(pkl, frame_ids):
             raise ValueError('stageii_vertices: frame_ids must be a list of integers')
         if len(ids) and (ids.min() < 0 or ids.max() >= T):
             raise IndexError(f'stageii_vertices: frame_ids outside the {T} solved frames')
-    return sm, mp, kind, start, count, ids
+    return _StageIIPlan(sm, mp, kind, start, count, ids)
 
 
 def _stageii_load(stageii_data_or_fname):
@@ -383,6 +389,61 @@ def _stageii_device(surface_model, shapedirs, b, kind, start, count):
     return dev
 
 
+def _need_model_faces(who, surface_model):
+    if getattr(surface_model, 'f', None) is None:
+        what = 'return_normals needs a surface model with faces (f)' if who == 'stageii_vertices' else 'the surface model has no faces (f)'
+        raise ValueError(f'{who}: {what}')
+
+
+def _need_model_vertices(vids, surface_model):
+    if len(vids) and vids.max() >= surface_model.V:
+        raise ValueError(f'stageii_virtual_markers: vertex ids beyond the {surface_model.V} vertices of the model')
+
+
+@contextmanager
+def _stageii_session(pkl, plan, surface_model, who, faces=False, vids=None):
+    """The model handle of a planned export, open for the `with` block: (handle, surface model (loaded from the stored cfg where none is
+    given), fullpose[ids], trans[ids], coefficients[ids] | None).  faces: the model must bring its triangles, which the handle then
+    holds; vids: vertex ids that must lie on the model.  Both are refused before a device is touched."""
+    surface_model, shapedirs, b, fullpose, trans, coef = _stageii_export_inputs(pkl, plan, surface_model)
+    if faces:
+        _need_model_faces(who, surface_model)
+    if vids is not None:
+        _need_model_vertices(vids, surface_model)
+    dev = _stageii_device(surface_model, shapedirs, b, plan.kind, plan.start, plan.count)
+    try:
+        if faces:
+            dev.set_faces(surface_model.f)
+        yield dev, surface_model, fullpose, trans, coef
+    finally:
+        dev.close()
+
+
+def _observed_points(pkl, ids, who, required, with_simulated=False):
+    """(labels, observed[len(ids), M, 3], simulated[len(ids), M, 3] | None): the ragged markers_obs (and, with_simulated, markers_sim) of
+    a Stage-II result on the rows `ids`, laid out over latent_labels -- or, without them, the labels in the order the frames first name
+    them -- NaN where a label is not observed.  A result without markers_obs / labels_obs: a KeyError if they are `required`, no points
+    otherwise."""
+    dbg = pkl['stageii_debug_details']
+    src = dbg if 'markers_obs' in dbg else pkl          # (load_as_amass_npz(include_markers=True) lifts them to the top level)
+    for k in ('markers_obs', 'labels_obs'):
+        if k not in src:
+            if required:
+                raise KeyError(f"{who}: the Stage-II data has no '{k}'")
+            return [], np.zeros((len(ids), 0, 3)), None
+    T = np.asarray(pkl['fullpose']).shape[0]
+    if len(src['markers_obs']) != T or len(src['labels_obs']) != T:
+        raise ValueError(f"{who}: markers_obs / labels_obs hold {len(src['markers_obs'])} / {len(src['labels_obs'])} frames, the result {T}")
+    labels = list(pkl['latent_labels']) if 'latent_labels' in pkl else list(dict.fromkeys(l for row in src['labels_obs'] for l in row))
+    from .chmosh import pack_observed_markers
+    try:
+        obs = pack_observed_markers(src['markers_obs'], src['labels_obs'], labels, ids)
+        sim = pack_observed_markers(src['markers_sim'], src['labels_obs'], labels, ids) if with_simulated and 'markers_sim' in src else None
+    except ValueError as e:
+        raise ValueError(f'{who}: {e}') from None
+    return labels, obs, sim
+
+
 def stageii_vertices(stageii_data_or_fname, surface_model=None, frame_ids=None, dtype=np.float32, return_normals=False):
     """verts[T, V, 3]: the meshes a Stage-II result (pickle file name or dict) describes, frame by frame -- pose, translation,
     Stage-I betas AND, where the solve freed them, the per-frame expression (optimize_face, SMPL-X) or DMPL coefficients
@@ -397,20 +458,11 @@ def stageii_vertices(stageii_data_or_fname, surface_model=None, frame_ids=None, 
     the device from the exported buffer (the model needs its triangles `f`)."""
     pkl = _stageii_load(stageii_data_or_fname)
     plan = _stageii_vertices_plan(pkl, frame_ids)
-    if return_normals and surface_model is not None and getattr(surface_model, 'f', None) is None:
-        raise ValueError('stageii_vertices: return_normals needs a surface model with faces (f)')
-    sm, mp, kind, start, count, ids = plan
-    surface_model, shapedirs, b, fullpose, trans, coef = _stageii_export_inputs(pkl, plan, surface_model)
-    if return_normals and getattr(surface_model, 'f', None) is None:
-        raise ValueError('stageii_vertices: return_normals needs a surface model with faces (f)')
-    dev = _stageii_device(surface_model, shapedirs, b, kind, start, count)
-    try:
-        if not return_normals:
-            return dev.lbs_forward(fullpose, trans, dtype=dtype, shape=coef)
-        dev.set_faces(surface_model.f)
-        return dev.lbs_forward_with_normals(fullpose, trans, dtype=dtype, shape=coef)
-    finally:
-        dev.close()
+    if return_normals and surface_model is not None:
+        _need_model_faces('stageii_vertices', surface_model)
+    with _stageii_session(pkl, plan, surface_model, 'stageii_vertices', faces=return_normals) as (dev, _, fullpose, trans, coef):
+        export = dev.lbs_forward_with_normals if return_normals else dev.lbs_forward
+        return export(fullpose, trans, dtype=dtype, shape=coef)
 
 
 DEFAULT_M2B_DISTANCE = 0.0095     # prepare_mosh_markers_latent's default distance from skin (chmosh.py:59)
@@ -452,19 +504,16 @@ def _stageii_virtual_markers_plan(pkl, marker_layout, surface_model, frame_ids, 
     """Every refusal of stageii_virtual_markers that needs no model file and no device."""
     plan = _stageii_vertices_plan(pkl, frame_ids)
     labels, vids, m2b, layout_type = _virtual_marker_layout(marker_layout)
-    sm = plan[0]
-    if layout_type is not None and layout_type != sm['type']:
-        raise ValueError(f"stageii_virtual_markers: the layout is for {layout_type}, the Stage-II result for {sm['type']}")
+    if layout_type is not None and layout_type != plan.sm['type']:
+        raise ValueError(f"stageii_virtual_markers: the layout is for {layout_type}, the Stage-II result for {plan.sm['type']}")
     if out_fname is not None and not str(out_fname).endswith(('.c3d', '.npz')):
         raise ValueError(f'stageii_virtual_markers: out_fname must end in .c3d or .npz: {out_fname}')
     if out_fname is not None and 'mocap_frame_rate' not in pkl['stageii_debug_details']:
         raise KeyError("stageii_virtual_markers: the Stage-II data stores no frame rate (stageii_debug_details['mocap_frame_rate']) "
                        "to write the file with")
     if surface_model is not None:
-        if getattr(surface_model, 'f', None) is None:
-            raise ValueError('stageii_virtual_markers: the surface model has no faces (f)')
-        if len(vids) and vids.max() >= surface_model.V:
-            raise ValueError(f'stageii_virtual_markers: vertex ids beyond the {surface_model.V} vertices of the model')
+        _need_model_faces('stageii_virtual_markers', surface_model)
+        _need_model_vertices(vids, surface_model)
     return plan, labels, vids, m2b
 
 
@@ -480,18 +529,8 @@ def stageii_virtual_markers(stageii_data_or_fname, marker_layout, surface_model=
     Stage-II result stores (a result without one is a KeyError, raised before any work)."""
     pkl = _stageii_load(stageii_data_or_fname)
     plan, labels, vids, m2b = _stageii_virtual_markers_plan(pkl, marker_layout, surface_model, frame_ids, out_fname)
-    sm, mp, kind, start, count, ids = plan
-    surface_model, shapedirs, b, fullpose, trans, coef = _stageii_export_inputs(pkl, plan, surface_model)
-    if getattr(surface_model, 'f', None) is None:
-        raise ValueError('stageii_virtual_markers: the surface model has no faces (f)')
-    if len(vids) and vids.max() >= surface_model.V:
-        raise ValueError(f'stageii_virtual_markers: vertex ids beyond the {surface_model.V} vertices of the model')
-    dev = _stageii_device(surface_model, shapedirs, b, kind, start, count)
-    try:
-        dev.set_faces(surface_model.f)
+    with _stageii_session(pkl, plan, surface_model, 'stageii_virtual_markers', faces=True, vids=vids) as (dev, _, fullpose, trans, coef):
         markers = dev.virtual_markers(fullpose, trans, vids, m2b, dtype=dtype, shape=coef)
-    finally:
-        dev.close()
     if out_fname is not None:
         rate = float(pkl['stageii_debug_details']['mocap_frame_rate'])
         if str(out_fname).endswith('.c3d'):
@@ -505,26 +544,9 @@ def stageii_virtual_markers(stageii_data_or_fname, marker_layout, surface_model=
 def _stageii_marker_skin_distance_plan(pkl, surface_model, frame_ids):
     """Every refusal of stageii_marker_skin_distance that needs no model file and no device; (plan, labels, points[T, M, 3])."""
     plan = _stageii_vertices_plan(pkl, frame_ids)
-    dbg = pkl['stageii_debug_details']
-    src = dbg if 'markers_obs' in dbg else pkl          # (load_as_amass_npz(include_markers=True) lifts them to the top level)
-    for k in ('markers_obs', 'labels_obs'):
-        if k not in src:
-            raise KeyError(f"stageii_marker_skin_distance: the Stage-II data has no '{k}'")
-    T = np.asarray(pkl['fullpose']).shape[0]
-    if len(src['markers_obs']) != T or len(src['labels_obs']) != T:
-        raise ValueError(f"stageii_marker_skin_distance: markers_obs / labels_obs hold {len(src['markers_obs'])} / {len(src['labels_obs'])} "
-                         f"frames, the result {T}")
-    if surface_model is not None and getattr(surface_model, 'f', None) is None:
-        raise ValueError('stageii_marker_skin_distance: the surface model has no faces (f)')
-    if 'latent_labels' in pkl:
-        labels = list(pkl['latent_labels'])
-    else:                                                # the labels in the order the frames first name them
-        labels = list(dict.fromkeys(l for row in src['labels_obs'] for l in row))
-    from .chmosh import pack_observed_markers
-    try:
-        points = pack_observed_markers(src['markers_obs'], src['labels_obs'], labels, plan[5])
-    except ValueError as e:
-        raise ValueError(f'stageii_marker_skin_distance: {e}') from None
+    labels, points, _ = _observed_points(pkl, plan.ids, 'stageii_marker_skin_distance', required=True)
+    if surface_model is not None:
+        _need_model_faces('stageii_marker_skin_distance', surface_model)
     return plan, labels, points
 
 
@@ -540,18 +562,10 @@ def stageii_marker_skin_distance(stageii_data_or_fname, surface_model=None, fram
     negative_share) over the label's observed frames.  surface_model / frame_ids / dtype: as in stageii_vertices."""
     pkl = _stageii_load(stageii_data_or_fname)
     plan, labels, points = _stageii_marker_skin_distance_plan(pkl, surface_model, frame_ids)
-    sm, mp, kind, start, count, ids = plan
-    surface_model, shapedirs, b, fullpose, trans, coef = _stageii_export_inputs(pkl, plan, surface_model)
-    if getattr(surface_model, 'f', None) is None:
-        raise ValueError('stageii_marker_skin_distance: the surface model has no faces (f)')
-    dev = _stageii_device(surface_model, shapedirs, b, kind, start, count)
-    try:
-        dev.set_faces(surface_model.f)
+    with _stageii_session(pkl, plan, surface_model, 'stageii_marker_skin_distance', faces=True) as (dev, _, fullpose, trans, coef):
         res = dev.marker_surface_distance(fullpose, trans, points, shape=coef, dtype=dtype)
-    finally:
-        dev.close()
     from .chmosh import skin_distance_summary
-    return dict(labels=labels, distance=res.distance, face=res.face, part=res.part, frame_ids=np.asarray(ids),
+    return dict(labels=labels, distance=res.distance, face=res.face, part=res.part, frame_ids=np.asarray(plan.ids),
                 summary=skin_distance_summary(res.distance, labels))
 
 
@@ -582,18 +596,13 @@ def stageii_joints(stageii_data_or_fname, surface_model=None, frame_ids=None, dt
     out_fname: a '.npz' that receives the same entries; its directory is created, an existing file is refused (before any work)."""
     pkl = _stageii_load(stageii_data_or_fname)
     plan, rate = _stageii_joints_plan(pkl, frame_ids, out_fname)
-    sm, mp, kind, start, count, ids = plan
-    surface_model, shapedirs, b, fullpose, trans, coef = _stageii_export_inputs(pkl, plan, surface_model)
-    dev = _stageii_device(surface_model, shapedirs, b, kind, start, count)
-    try:
+    with _stageii_session(pkl, plan, surface_model, 'stageii_joints') as (dev, surface_model, fullpose, trans, coef):
         res = dev.posed_joints(fullpose, trans, shape=coef, dtype=dtype, return_rotations=return_rotations)
-    finally:
-        dev.close()
     out = dict(joints=res[0] if return_rotations else res)
     if return_rotations:
         out['rotations'] = res[1]
-    out.update(parents=np.asarray(surface_model.parents, dtype=np.int32), frame_ids=np.asarray(ids), mocap_frame_rate=rate,
-               surface_model_type=sm['type'])
+    out.update(parents=np.asarray(surface_model.parents, dtype=np.int32), frame_ids=np.asarray(plan.ids), mocap_frame_rate=rate,
+               surface_model_type=plan.sm['type'])
     if out_fname is not None:
         np.savez(_makepath(str(out_fname)), **out)
     return out
@@ -606,7 +615,7 @@ def _stageii_preview_plan(pkl, surface_model, frame_ids, out_dir, size, contact_
     """Every refusal of stageii_preview that needs no model file and no device; (plan, observed[T, M, 3], simulated[T, M, 3] or None,
     file names, contact-sheet file name or None)."""
     plan = _stageii_vertices_plan(pkl, frame_ids)
-    ids = plan[5]
+    ids = plan.ids
     try:
         W, H = (int(x) for x in size)
     except (TypeError, ValueError):
@@ -617,24 +626,9 @@ def _stageii_preview_plan(pkl, surface_model, frame_ids, out_dir, size, contact_
         raise ValueError(f'stageii_preview: contact_sheet_columns must be >= 1, got {contact_sheet_columns!r}')
     if len(ids) == 0:
         raise ValueError('stageii_preview: no frame to render')
-    if surface_model is not None and getattr(surface_model, 'f', None) is None:
-        raise ValueError('stageii_preview: the surface model has no faces (f)')
-    dbg = pkl['stageii_debug_details']
-    src = dbg if 'markers_obs' in dbg else pkl
-    T = np.asarray(pkl['fullpose']).shape[0]
-    obs, sim = np.zeros((len(ids), 0, 3)), None
-    if 'markers_obs' in src and 'labels_obs' in src:
-        if len(src['markers_obs']) != T or len(src['labels_obs']) != T:
-            raise ValueError(f"stageii_preview: markers_obs / labels_obs hold {len(src['markers_obs'])} / {len(src['labels_obs'])} frames, "
-                             f"the result {T}")
-        labels = list(pkl['latent_labels']) if 'latent_labels' in pkl else list(dict.fromkeys(l for row in src['labels_obs'] for l in row))
-        from .chmosh import pack_observed_markers
-        try:
-            obs = pack_observed_markers(src['markers_obs'], src['labels_obs'], labels, ids)
-            if 'markers_sim' in src:
-                sim = pack_observed_markers(src['markers_sim'], src['labels_obs'], labels, ids)
-        except ValueError as e:
-            raise ValueError(f'stageii_preview: {e}') from None
+    if surface_model is not None:
+        _need_model_faces('stageii_preview', surface_model)
+    _, obs, sim = _observed_points(pkl, ids, 'stageii_preview', required=False, with_simulated=True)
     fnames, sheet = [], None
     if out_dir is not None:
         fnames = [osp.join(str(out_dir), 'frame_%06d.png' % int(f)) for f in ids]
@@ -662,26 +656,19 @@ def stageii_preview(stageii_data_or_fname, out_dir=None, surface_model=None, fra
     from . import preview, png_io
     pkl = _stageii_load(stageii_data_or_fname)
     plan, obs, sim, fnames, sheet_fname = _stageii_preview_plan(pkl, surface_model, frame_ids, out_dir, size, contact_sheet_columns)
-    sm, mp, kind, start, count, ids = plan
-    surface_model, shapedirs, b, fullpose, trans, coef = _stageii_export_inputs(pkl, plan, surface_model)
-    if getattr(surface_model, 'f', None) is None:
-        raise ValueError('stageii_preview: the surface model has no faces (f)')
+    ids = plan.ids
     points = obs if sim is None else np.concatenate([obs, sim], axis=1)
     N = points.shape[1]
     prgb = np.array([preview.OBSERVED_RGB] * obs.shape[1] + [preview.SIMULATED_RGB] * (N - obs.shape[1]), dtype=np.uint8).reshape(N, 3)
     W, H = int(size[0]), int(size[1])
     images = np.zeros((len(ids), H, W, 3), dtype=np.uint8)
-    dev = _stageii_device(surface_model, shapedirs, b, kind, start, count)
-    try:
-        dev.set_faces(surface_model.f)
+    with _stageii_session(pkl, plan, surface_model, 'stageii_preview', faces=True) as (dev, _, fullpose, trans, coef):
         camera = preview.preview_camera(dev.posed_joints(fullpose, trans, shape=coef), (W, H), view=view, up=up)
         for a in range(0, len(ids), PREVIEW_BATCH):
             z = slice(a, a + PREVIEW_BATCH)
             images[z] = dev.render_posed(fullpose[z], trans[z], camera, (W, H), points=points[z] if N else None, point_rgb=prgb if N else None,
                                          point_radius=float(marker_radius) if N else None, shape=None if coef is None else coef[z],
                                          outputs=('rgb',))['rgb']
-    finally:
-        dev.close()
     sheet = preview.contact_sheet(images, contact_sheet_columns) if contact_sheet_columns is not None else None
     for fn, img in zip(fnames, images):
         png_io.write_png(_makepath(fn), img)

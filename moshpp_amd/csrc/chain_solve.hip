@@ -18,8 +18,10 @@
 #include <type_traits>
 #if defined(__HIP_DEVICE_COMPILE__)
 #define MOSHII_OPAQUE(x) __asm__ __volatile__("" : "+v"(x))
+#define MOSHII_OPAQUE_S(x) __asm__ __volatile__("" : "+s"(x))   // (a wave-uniform value, in a scalar register)
 #else
 #define MOSHII_OPAQUE(x) do {} while (0)
+#define MOSHII_OPAQUE_S(x) do {} while (0)
 #endif
 __device__ __forceinline__ double uni64(double v) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -77,6 +79,37 @@ struct Ctx {
     double *big, *Jh, *Jrow, *Lm, *Trot, *xjs, *rest;
     int* tjs;
 };
+
+// The kernel body's own view of the LDS (k_chain_solve's frame loop with run_phase inlined): only what the frame loop and the dogleg
+// control touch.  A pointer the body holds is a scalar that lives across every call of the loop -- beyond the 108 scalar registers it is
+// parked in a lane of a vector register and fetched back at its use -- so the body keeps few: the five control vectors, the reduction
+// pad and the scalars lie back to back in the layout (make_layout: LDJ = 16 NBLK doubles apart, then 16 + 16) and so do the two column
+// tables; each group is ONE base, its members differ by compile-time constants that end up in the ds instructions' offset fields.
+// (The host refuses a layout without these distances: chain_layout_fault, moshii_dev.h.)  Everything else of Ctx is formed where it
+// is used: the phases and the out-of-line cold paths below make their own from the layout in the argument segment.
+struct BodyCtx {
+    double *pose, *trans, *pose_t, *trans_t, *pose_prev, *vtarget, *fullpose, *msim;
+    double *g, *dsd, *dgn, *ddl, *y, *red, *scal;   // g + {0, 1, 2, 3, 4} LDJ, g + 5 LDJ, g + 5 LDJ + 16
+    int *visidx, *colpid, *colprior, *colq;         // colprior = colpid + LDJ
+};
+template <int NBLK>
+__device__ __forceinline__ BodyCtx make_body_ctx(double* lds, const ChainLayout& ly) {
+    constexpr int LDJ = 16 * NBLK;
+    // (each offset a scalar of its own: as an element of the register tuple the layout was loaded in, it kept the whole tuple alive --
+    //  sixteen lanes fetched back for one offset, at every call of the loop)
+    auto at = [&](int off) { MOSHII_OPAQUE_S(off); return lds + off; };
+    BodyCtx cx;
+    cx.pose = at(ly.o_pose); cx.trans = at(ly.o_trans); cx.pose_t = at(ly.o_pose_t); cx.trans_t = at(ly.o_trans_t);
+    cx.pose_prev = at(ly.o_pose_prev); cx.vtarget = at(ly.o_vtarget); cx.fullpose = at(ly.o_fullpose); cx.msim = at(ly.o_msim);
+    double* ctl = at(ly.o_g);
+    cx.g = ctl; cx.dsd = ctl + LDJ; cx.dgn = ctl + 2 * LDJ; cx.ddl = ctl + 3 * LDJ; cx.y = ctl + 4 * LDJ;
+    cx.red = ctl + 5 * LDJ; cx.scal = ctl + 5 * LDJ + 16;
+    int* ints = reinterpret_cast<int*>(at(ly.o_ints));
+    auto iat = [&](int off) { MOSHII_OPAQUE_S(off); return ints + off; };
+    cx.visidx = iat(ly.i_visidx); cx.colq = iat(ly.i_colq);
+    cx.colpid = iat(ly.i_colpid); cx.colprior = cx.colpid + LDJ;
+    return cx;
+}
 
 struct FrameParams {
     const double* obs;      // [M][3] of this frame
@@ -274,7 +307,8 @@ template <bool L2> __device__ __forceinline__ unsigned coop_ld32(MOSHII_GP(unsig
 #endif
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ unsigned coop_begin(const Ctx& cx) { return (unsigned)__builtin_amdgcn_readfirstlane((int)cx.scal[S_COOP_SEQ]) + 1u; }   // (a scalar)
+template <class C>
+__device__ __forceinline__ unsigned coop_begin(const C& cx) { return (unsigned)__builtin_amdgcn_readfirstlane((int)cx.scal[S_COOP_SEQ]) + 1u; }   // (a scalar)
 __device__ __forceinline__ MOSHII_GP(unsigned long long) coop_slot(const CoopCtx& co, unsigned seq, int r) {
     return co.slots + ((size_t)(seq & 1u) * co.G + r) * co.slot_doubles;
 }
@@ -321,8 +355,8 @@ __device__ __forceinline__ void coop_skew(const CoopCtx& co, unsigned seq) {
     }
 }
 // All threads call, after their payload stores: publish this rank's slot, wait for every rank's.  false: the group is broken.
-template <bool L2 = false>
-__device__ __forceinline__ bool coop_publish_wait(const CoopCtx& co, const Ctx& cx, unsigned seq) {
+template <bool L2 = false, class C>
+__device__ __forceinline__ bool coop_publish_wait(const CoopCtx& co, const C& cx, unsigned seq) {
     const int tid = threadIdx.x;
     coop_skew(co, seq);
     PROF_T(_tp0);
@@ -364,7 +398,8 @@ __device__ __forceinline__ bool coop_publish_wait(const CoopCtx& co, const Ctx& 
     return cx.scal[S_COOP_FAIL] == 0.0;
 }
 // All threads call once they have read what they need of the other ranks' slots.
-__device__ __forceinline__ void coop_end(const Ctx& cx, unsigned seq) {
+template <class C>
+__device__ __forceinline__ void coop_end(const C& cx, unsigned seq) {
     __syncthreads();
     if (threadIdx.x == 0) cx.scal[S_COOP_SEQ] = (double)seq;
     __syncthreads();
@@ -372,8 +407,8 @@ __device__ __forceinline__ void coop_end(const Ctx& cx, unsigned seq) {
 // A few numbers per rank (NS <= 4 doubles): 8-byte {tag = sequence number, half a double} granules in the last 32 words of the slot --
 // the data is its own flag (Guideline 16, form R2): no drain, no flag hop; a reader polls the granule until its tag is this exchange's.
 // All threads call; on return land[r * NS + k] (LDS) holds value k of rank r.  Follow with coop_end().
-template <int NS, bool L2>
-__device__ __forceinline__ bool coop_exchange_small_(const CoopCtx& co, const Ctx& cx, unsigned seq, const double (&mine)[NS], double* land) {
+template <int NS, bool L2, class C>
+__device__ __forceinline__ bool coop_exchange_small_(const CoopCtx& co, const C& cx, unsigned seq, const double (&mine)[NS], double* land) {
     const int tid = threadIdx.x;
     const int goff = co.slot_doubles - 32;
     coop_skew(co, seq);
@@ -407,8 +442,8 @@ __device__ __forceinline__ bool coop_exchange_small_(const CoopCtx& co, const Ct
     TRACE_STAMP(co, seq, 2);
     return cx.scal[S_COOP_FAIL] == 0.0;
 }
-template <int NS>
-__device__ __forceinline__ bool coop_exchange_small(const CoopCtx& co, const Ctx& cx, unsigned seq, const double (&mine)[NS], double* land) {
+template <int NS, class C>
+__device__ __forceinline__ bool coop_exchange_small(const CoopCtx& co, const C& cx, unsigned seq, const double (&mine)[NS], double* land) {
     return coop_exchange_small_<NS, false>(co, cx, seq, mine, land);
 }
 
@@ -2624,6 +2659,15 @@ __device__ __forceinline__ KArgsPtr kargs_of(const KernelCtx* kc) {
 #else
 #define MOSHII_CTX_FROM_KARGS(kc) const ChainLayout ly = uniform_load(&(kc)->ly); const ModelDev md = uniform_load(&(kc)->md); const PriorDev pr = uniform_load(&(kc)->pr); const OptsDev op = uniform_load(&(kc)->op);
 #endif
+// The kernel body's handle on the same descriptors: ka->ly / ka->md / ka->op read a field with a scalar load at its use (host emulation:
+// from the KernelCtx copy, whose members have the same names).  Valid once the KernelCtx is written (the barrier behind the chain's set-up).
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(MOSHII_NO_KARGS)
+typedef KArgsPtr BodyArgs;
+__device__ __forceinline__ BodyArgs body_args(const KernelCtx* kc) { return kargs_of(kc); }
+#else
+typedef const KernelCtx* BodyArgs;
+__device__ __forceinline__ BodyArgs body_args(const KernelCtx* kc) { return kc; }
+#endif
 
 // Cooperative assembly, large matrices (assemble(): the reduce-scatter + all-gather form), after the wait of exchange `seq` in which
 // every rank posted its partial products: this rank sums its tiles [rank TPR, (rank + 1) TPR) over the ranks -- in rank order, from zero:
@@ -2793,6 +2837,433 @@ __device__ __noinline__ void rigid_init_serial(const Ctx& cx, const FrameParams&
 }
 
 // ------------------------------------------------------------------------------------------------
+// The cold paths of the frame loop as functions of their own: each runs at most once per frame, most of them once per chain or per
+// chunk.  Inlined, their pointers, descriptor fields and temporaries shared the register allocation of the dogleg loop and stretched
+// live ranges over it; out of line each takes a few scalars and picks the rest up as the phases do -- layout, model and options from
+// the argument segment, attachment / frame parameters / rank from the KernelCtx -- so a call's prologue is paid where it does not count.
+// The statements are the ones the kernel body had.
+// ------------------------------------------------------------------------------------------------
+template <class T>
+__device__ __forceinline__ T* uniform_ptr(T* p) {   // (a pointer argument arrives in vector registers: back to a scalar pair)
+    const unsigned long long v = (unsigned long long)p;
+    return (T*)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)v));
+}
+
+// run_phase's rigid branch, cooperative chains: every rank needs all the simulated markers -- gather the ranks' rows (its own stay as they are)
+// (a function of its own: as a part of rigid_init_fn it took hipcc 7.2's register allocator down)
+__device__ __noinline__ void coop_gather_markers_fn() {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const KernelCtx* kc = reinterpret_cast<const KernelCtx*>(lds);
+    MOSHII_CTX_FROM_KARGS(kc)
+    const AttachDev at = uniform_load(&kc->at);
+    const Ctx cx = make_ctx(lds, ly);
+    const CoopCtx co = uniform_load(&kc->co);
+    const int tid = threadIdx.x;
+    {
+        const unsigned seq = coop_begin(cx);
+        auto gather = [&](auto l2) {   // (l2: the access scope, see coop_st_l2)
+            constexpr bool L2 = decltype(l2)::value;
+            auto* mine = coop_slot(co, seq, co.rank);
+            for (int i = 3 * co.mlo + tid; i < 3 * co.mhi; i += MOSHII_TPB) coop_st64<L2>(mine + i, f64_bits(cx.msim[i]));
+            if (tid == 0) coop_st64<L2>(mine + 3 * at.M, f64_bits((double)co.mlo));   // (where this rank's range starts)
+            if (coop_publish_wait<L2>(co, cx, seq)) {
+                const int M3 = 3 * at.M;
+                for (int i = tid; i < M3; i += MOSHII_TPB) {
+                    // owner of marker i / 3: the rank whose range holds it (ranges are contiguous and ascending: count the boundaries passed)
+                    int r = 0;
+                    for (int q = 1; q < co.G; ++q) r += (i >= 3 * (int)bits_f64(coop_ld64<L2>(coop_slot(co, seq, q) + 3 * at.M))) ? 1 : 0;
+                    if (r != co.rank) cx.msim[i] = bits_f64(coop_ld64<L2>(coop_slot(co, seq, r) + i));
+                }
+            }
+        };
+        gather(std::false_type());
+        coop_end(cx, seq);
+    }
+}
+// run_phase's rigid branch: rigid_transformations.py:72-83 on the markers just simulated, then the trial copy of the new point
+template <bool XT, bool COOP>
+__device__ __noinline__ void rigid_init_fn(const uint8_t* visrow) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const KernelCtx* kc = reinterpret_cast<const KernelCtx*>(lds);
+    MOSHII_CTX_FROM_KARGS(kc)
+    const AttachDev at = uniform_load(&kc->at);
+    const FrameParams fp = uniform_load(reinterpret_cast<const FrameParams*>(kc->fp_raw));
+    const Ctx cx = make_ctx(lds, ly);
+    const int tid = threadIdx.x;
+    const int NPX = XT ? ly.NPX : md.NP;
+    if constexpr (COOP) coop_gather_markers_fn();
+    if (tid == 0) rigid_init_serial(cx, fp, visrow, at.M);
+    __syncthreads();
+    for (int i = tid; i < NPX; i += MOSHII_TPB) cx.pose_t[i] = cx.pose[i];
+    if (tid < 3) cx.trans_t[tid] = cx.trans[tid];
+    __syncthreads();
+}
+
+// run_phase: column tables + needed-joint lists of a free set (Step 1's, or Step 2's: step2 != 0); they stay in LDS until a solve with
+// another set replaces them (body-only Stage-II uses one set throughout: built once per chain)
+template <bool XT>
+__device__ __noinline__ void column_tables_fn(int step2_) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const KernelCtx* kc = reinterpret_cast<const KernelCtx*>(lds);
+    MOSHII_CTX_FROM_KARGS(kc)
+    const Ctx cx = make_ctx(lds, ly);
+    const int tid = threadIdx.x;
+    const bool step2 = __builtin_amdgcn_readfirstlane(step2_) != 0;
+    const auto ids = step2 ? op.step2 : op.step1;
+    const int nids = step2 ? op.n2 : op.n1, nshp = (XT && step2) ? op.nshape : 0;
+    const int ncp = 3 + nids;
+    const int n = ncp + (XT ? nshp : 0);
+    for (int i = tid; i < md.NP; i += MOSHII_TPB) cx.colq[i] = -1;
+    __syncthreads();
+    for (int q = tid; q < n; q += MOSHII_TPB) {
+        const int pid = (q < 3) ? -1 : ((q < ncp) ? ids[q - 3] : md.NP + (q - ncp));
+        cx.colpid[q] = pid;
+        cx.colprior[q] = (pid >= 0 && pid < md.NP) ? cx.pid2prior[pid] : -1;
+        if (pid >= 0 && pid < md.NP) cx.colq[pid] = q;
+    }
+    if (tid == 0) {
+        for (int k = 0; k < md.K; ++k) cx.jointslot[k] = -1;
+        for (int i = 0; i < nids; ++i) {
+            const int pid = ids[i];
+            if (pid < md.body_dof) cx.jointslot[pid / 3] = 0;
+            else for (int k = md.body_dof / 3; k < md.K; ++k) cx.jointslot[k] = 0;
+        }
+        int c = 0;
+        for (int k = 0; k < md.K; ++k) if (cx.jointslot[k] == 0) { cx.jointslot[k] = c; cx.kfree[c] = k; ++c; }
+        cx.scal[S_TMP0] = (double)c;
+        int nh = 0;   // ids are sorted, so the hand-PCA coefficients (pid >= body_dof) are the trailing columns
+        for (int i = 0; i < nids; ++i) nh += (ids[i] >= md.body_dof) ? 1 : 0;
+        cx.scal[S_TMP2] = (double)nh;
+        // joints whose rotation moves during this solve (their pose correctives are re-summed at every evaluation)
+        // and the rest (summed once into cx.vconst); the root has no correctives
+        int ns = 0, nc = 0;
+        for (int k = 1; k < md.K; ++k) { if (cx.jointslot[k] >= 0) cx.ksum[ns++] = k; else cx.kconst[nc++] = k; }
+        cx.scal[S_TMP3] = (double)ns;
+    }
+    __syncthreads();
+}
+
+// run_phase: cx.vconst = v_shaped + correctives of the joints that stay fixed in this solve, at the current pose.  It stays valid until
+// a solve with a different free set runs (body-only Stage-II: computed once per chain).
+template <bool COOP>
+__device__ __noinline__ void vconst_fn(int nkc_) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const KernelCtx* kc = reinterpret_cast<const KernelCtx*>(lds);
+    MOSHII_CTX_FROM_KARGS(kc)
+    const AttachDev at = uniform_load(&kc->at);
+    const Ctx cx = make_ctx(lds, ly);
+    CoopCtx co = CoopCtx();
+    if constexpr (COOP) co = uniform_load(&kc->co);
+    const int tid = threadIdx.x;
+    const int nkc = __builtin_amdgcn_readfirstlane(nkc_);
+    for (int d = tid; d < md.P; d += MOSHII_TPB) cx.fullpose[d] = fullpose_entry(md, cx.pose, d);
+    __syncthreads();
+    if (tid < md.K) {
+        double R[9];
+        rodrigues_R(&cx.fullpose[3 * tid], R);
+#pragma unroll
+        for (int e = 0; e < 9; ++e) cx.feat[tid * 9 + e] = R[e] - ((e == 0 || e == 4 || e == 8) ? 1.0 : 0.0);
+    }
+    __syncthreads();
+    if constexpr (COOP) posedirs_partial_range(cx, at, cx.kconst, nkc, at.vsh, cx.vconst, 3 * co.mlo, 3 * co.mhi);
+    else posedirs_partial(cx, at, cx.kconst, nkc, at.vsh, cx.vconst);
+    __syncthreads();
+}
+
+// The chunk protocol at the head of a frame (moshii_sequence_solve's chunked solves; ChainDev has the rules).  st: has_prev | first << 1.
+// A cooperative repair chain, rank 0's part of the verdict block (all of rank 0's threads call): the previous frame's re-join verdict, a
+// chunk boundary with its baton negotiation, an upstream chain's request for this territory.  Returns bi_next << 1 | halt.
+__device__ __noinline__ int coop_lead_verdict_fn(const ChainDev* chp_, int t_, int rejoin_run_, int bi_next_, int st_) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const KernelCtx* kc = reinterpret_cast<const KernelCtx*>(lds);
+    MOSHII_CTX_FROM_KARGS(kc)
+    const Ctx cx = make_ctx(lds, ly);
+    const int tid = threadIdx.x;
+    const ChainDev* chp = uniform_ptr(chp_);
+    const int t = __builtin_amdgcn_readfirstlane(t_), rejoin_run = __builtin_amdgcn_readfirstlane(rejoin_run_), stf = __builtin_amdgcn_readfirstlane(st_);
+    int bi_next = __builtin_amdgcn_readfirstlane(bi_next_);
+    const bool has_prev = (stf & 1) != 0, first = (stf & 2) != 0;
+    const int NP = md.NP, F = chp->F;
+    bool halt = false;
+    const int S = 2 * NP + 5;
+    if (rejoin_run >= 2 && t < F) {   // the previous frame's verdict: pose and pose_prev both match, the stored rows (and final state) stand
+        if (tid == 0 && chp->frames_done) *chp->frames_done = t;
+        halt = true;
+    }
+    if (!halt && bi_next < chp->nb && t == chp->bnd[bi_next] - chp->bnd_off) {   // a chunk boundary (see the plain chain: chunk_boundary_fn)
+        double* s1 = chp->run_final + (size_t)bi_next * S;
+        for (int i = tid; i < NP; i += MOSHII_TPB) { s1[i] = cx.pose[i]; s1[NP + i] = cx.pose_prev[i]; }
+        if (tid < 3) s1[2 * NP + tid] = cx.trans[tid];
+        if (tid == 3) s1[2 * NP + 3] = has_prev ? 1.0 : 0.0;
+        if (tid == 4) s1[2 * NP + 4] = first ? 1.0 : 0.0;
+        if (chp->baton != nullptr) {
+            if (tid == 0) {
+                int* st = chp->baton + 2 * (chp->chunk0 + 1 + bi_next);
+                double go = 1.0;
+                if (__hip_atomic_load(st, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 1) {
+                    __hip_atomic_store(st + 1, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+                    int spins = 0;
+                    while (__hip_atomic_load(st, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 2) {
+                        __builtin_amdgcn_s_sleep(64);
+                        if (++spins > 20000) { go = 0.0; break; }
+                    }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                cx.scal[S_BATON] = go;
+            }
+            __syncthreads();
+            if (cx.scal[S_BATON] == 0.0) { if (tid == 0 && chp->frames_done) *chp->frames_done = t; halt = true; }
+            __syncthreads();
+        }
+        if (!halt) {
+            double* s2 = chp->run_entry + (size_t)(bi_next + 1) * S;
+            for (int i = tid; i < NP; i += MOSHII_TPB) { s2[i] = cx.pose[i]; s2[NP + i] = cx.pose_prev[i]; }
+            if (tid < 3) s2[2 * NP + tid] = cx.trans[tid];
+            if (tid == 3) s2[2 * NP + 3] = has_prev ? 1.0 : 0.0;
+            if (tid == 4) s2[2 * NP + 4] = first ? 1.0 : 0.0;
+            ++bi_next;
+        }
+    }
+    if (!halt && chp->baton != nullptr && t < F) {   // has an upstream chain of this round asked for this chain's territory?
+        if (tid == 0) cx.scal[S_ABORT] = (double)__hip_atomic_load(&chp->baton[2 * chp->chunk0 + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        if (cx.scal[S_ABORT] != 0.0) {
+            if (tid == 0) {
+                chp->run_entry[(size_t)bi_next * S + 2 * NP + 3] = MOSHII_MARK_ENTRY_SPOILED;
+                int* mark = chp->abort_at + chp->chunk0 + bi_next;
+                if (*mark < chp->bnd_off + t) *mark = chp->bnd_off + t;
+                if (chp->frames_done) *chp->frames_done = -t - 1;
+            }
+            halt = true;
+        }
+        __syncthreads();
+    }
+    return (bi_next << 1) | (halt ? 1 : 0);
+}
+
+// A pass-1 chain that checks its own right-hand hand-off (ChainDev::fuse_F), at the frames where it has something to say: t == skip
+// (the entry state is out), t == F of a chain without a right neighbour, t == fuse_F (the end of its own chunk: carry on as the repair
+// chain of the next chunk, or stop).  Returns 0: go on as before, 1: the chain ends here, 2: it carries on (fuse_on).
+template <bool XT>
+__device__ __noinline__ int carry_on_fn(const ChainDev* chp_, int t_, int st_) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const KernelCtx* kc = reinterpret_cast<const KernelCtx*>(lds);
+    MOSHII_CTX_FROM_KARGS(kc)
+    const Ctx cx = make_ctx(lds, ly);
+    const int tid = threadIdx.x;
+    const ChainDev* chp = uniform_ptr(chp_);
+    const int t = __builtin_amdgcn_readfirstlane(t_), stf = __builtin_amdgcn_readfirstlane(st_);
+    const bool has_prev = (stf & 1) != 0, first = (stf & 2) != 0;
+    const int NP = md.NP, F = chp->F, skip = chp->skip;
+    const int S = 2 * NP + 5 + (XT ? op.nshape : 0);
+    if (t == skip && chp->entry_state != nullptr) {   // the entry state is out: the left neighbour may compare with it
+        __syncthreads();
+        if (tid == 0) { __threadfence(); __hip_atomic_store(&chp->fuse_flags[3 * chp->fuse_c], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
+    }
+    if (chp->fuse_F == 0 && t == F) {                  // (a chain without a right neighbour: its rows are complete ...
+        __syncthreads();
+        if (tid == 0) {
+            __threadfence();
+            __hip_atomic_store(&chp->fuse_flags[3 * chp->fuse_c + 1], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            // ... and it never carries on: its verdict is final too.  The chain of the chunk before it waits for BOTH flags
+            // before it takes this chunk over; without this store it waited out its whole patience and left the
+            // last chunk of every sequence to a host round.)
+            __hip_atomic_store(&chp->fuse_flags[3 * chp->fuse_c + 2], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    if (chp->fuse_F > 0 && t == chp->fuse_F) {
+        // The end of this chain's own chunk (ChainDev::fuse_F): its end state ...
+        double* sf = chp->run_final - S;
+        for (int i = tid; i < NP; i += MOSHII_TPB) { sf[i] = cx.pose[i]; sf[NP + i] = cx.pose_prev[i]; }
+        if (tid < 3) sf[2 * NP + tid] = cx.trans[tid];
+        if (tid == 3) sf[2 * NP + 3] = has_prev ? 1.0 : 0.0;
+        if (tid == 4) sf[2 * NP + 4] = first ? 1.0 : 0.0;
+        if constexpr (XT) for (int e = tid; e < op.nshape; e += MOSHII_TPB) sf[2 * NP + 5 + e] = cx.pose[NP + e];
+        __syncthreads();
+        if (tid == 0) { __threadfence(); __hip_atomic_store(&chp->fuse_flags[3 * chp->fuse_c + 1], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }   // this chunk's rows are complete
+        // ... against the entry state the next chunk's chain recorded a chunk ago (it only has to be waited for when the
+        // chunks are not all resident -- then this chain gives up quickly and the host's rounds do the rest)
+        bool carry = false;
+        auto state_dev = [&](const double* en) {   // max |this chain's state - en| (flags must be equal; NaN counts as a miss)
+            double dv = 0.0, nn = 0.0;
+            for (int i = tid; i < NP; i += MOSHII_TPB) { dv = fmax(dv, fmax(fabs(cx.pose[i] - en[i]), fabs(cx.pose_prev[i] - en[NP + i]))); nn += en[i] + en[NP + i]; }
+            if (tid < 3) dv = fmax(dv, fabs(cx.trans[tid] - en[2 * NP + tid]));
+            if (tid == 3 && (has_prev ? 1.0 : 0.0) != en[2 * NP + 3]) dv = MOSHII_HANDOFF_MISMATCH;
+            if (tid == 4 && (first ? 1.0 : 0.0) != en[2 * NP + 4]) dv = MOSHII_HANDOFF_MISMATCH;
+            if constexpr (XT) for (int e = tid; e < op.nshape; e += MOSHII_TPB) dv = fmax(dv, fabs(cx.pose[NP + e] - en[2 * NP + 5 + e]));
+            if (!(nn == nn)) dv = MOSHII_HANDOFF_MISMATCH;
+            return block_max(dv, cx.red);
+        };
+        auto wait_flag = [&](int* fl, int patience) {   // thread 0 waits (bounded) for *fl == 1; every thread gets the outcome
+            if (tid == 0) {
+                double go = 1.0;
+                int spins = 0;
+                while (__hip_atomic_load(fl, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 1) {
+                    __builtin_amdgcn_s_sleep(64);
+                    if (++spins > patience) { go = 0.0; break; }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                cx.scal[S_BATON] = go;
+            }
+            __syncthreads();
+            const bool ok_ = cx.scal[S_BATON] != 0.0;
+            __syncthreads();
+            return ok_;
+        };
+        if (chp->fuse_has_next && wait_flag(chp->fuse_flags + 3 * (chp->fuse_c + 1), 2000)) {
+            const double dv = state_dev(chp->run_entry);
+            carry = !(dv <= chp->fuse_tol);
+            // A gross miss (another basin) is only this chain's to repair if its OWN chunk stands on firm ground: if the hand-off
+            // INTO this chunk missed grossly too, this chain's state is the suspect one and the sweep that repairs this chunk
+            // will deal with the next boundary when it gets there (the rule the host applies to its repair rounds).  The left
+            // neighbour finishes at about the same time; if it has not, the chain goes ahead.
+            if (carry && dv > 1e-6 && chp->fuse_has_prev && wait_flag(chp->fuse_flags + 3 * (chp->fuse_c - 1) + 1, 150)) {
+                const double* lf = chp->run_final - 2 * S;   // end state of the left neighbour
+                const double* oe = chp->run_entry - S;       // the entry state this chain recorded
+                double dl = 0.0;
+                for (int i = tid; i < 2 * NP + 3; i += MOSHII_TPB) dl = fmax(dl, fabs(lf[i] - oe[i]));
+                dl = block_max(dl, cx.red);
+                if (!(dl <= 1e-6)) carry = false;
+            }
+        }
+        // The verdict (a chain will start at the next chunk, or not) is in place before it is declared final: a sweep
+        // arriving at the next boundary waits for that declaration before it looks.
+        if (carry && tid == 0) __hip_atomic_store(&chp->baton[2 * chp->chunk0], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        if (tid == 0) { __threadfence(); __hip_atomic_store(&chp->fuse_flags[3 * chp->fuse_c + 2], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
+        if (!carry) { if (tid == 0 && chp->frames_done) *chp->frames_done = t; return 1; }
+        // Carry on as the repair chain of the next chunk -- once that chunk's own chain has written its last row (from here on
+        // its rows are compared against and replaced), unless an upstream sweep asks for this territory meanwhile.
+        if (tid == 0) {
+            int* fl = chp->fuse_flags + 3 * (chp->fuse_c + 1) + 1;
+            double go = 1.0;
+            int spins = 0;
+            // (... AND has given its own verdict: until then it may still read the entry state it recorded -- the slot written
+            //  below -- for its "is my own chunk on firm ground" test; overwriting it earlier made that test compare this
+            //  chain's end state with itself)
+            while (__hip_atomic_load(fl, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 1 ||
+                   __hip_atomic_load(fl + 1, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 1) {
+                if (__hip_atomic_load(&chp->baton[2 * chp->chunk0 + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) { go = 0.0; break; }
+                __builtin_amdgcn_s_sleep(64);
+                if (++spins > 20000) { go = 0.0; break; }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            if (go != 0.0 && chp->fuse_count != nullptr) atomicAdd(chp->fuse_count, 1);
+            cx.scal[S_BATON] = go;
+        }
+        __syncthreads();
+        if (cx.scal[S_BATON] == 0.0) { if (tid == 0 && chp->frames_done) *chp->frames_done = t; return 1; }
+        double* s2 = chp->run_entry;   // the next chunk is entered with this state
+        for (int i = tid; i < NP; i += MOSHII_TPB) { s2[i] = cx.pose[i]; s2[NP + i] = cx.pose_prev[i]; }
+        if (tid < 3) s2[2 * NP + tid] = cx.trans[tid];
+        if (tid == 3) s2[2 * NP + 3] = has_prev ? 1.0 : 0.0;
+        if (tid == 4) s2[2 * NP + 4] = first ? 1.0 : 0.0;
+        if constexpr (XT) for (int e = tid; e < op.nshape; e += MOSHII_TPB) s2[2 * NP + 5 + e] = cx.pose[NP + e];
+        return 2;
+    }
+    return 0;
+}
+
+// A chunk boundary inside a run-through repair chain (plain chains; bi_next: the boundary's index).  Returns 0 if the chain ends here.
+template <bool XT>
+__device__ __noinline__ int chunk_boundary_fn(const ChainDev* chp_, int t_, int bi_next_, int st_) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const KernelCtx* kc = reinterpret_cast<const KernelCtx*>(lds);
+    MOSHII_CTX_FROM_KARGS(kc)
+    const Ctx cx = make_ctx(lds, ly);
+    const int tid = threadIdx.x;
+    const ChainDev* chp = uniform_ptr(chp_);
+    const int t = __builtin_amdgcn_readfirstlane(t_), bi_next = __builtin_amdgcn_readfirstlane(bi_next_), stf = __builtin_amdgcn_readfirstlane(st_);
+    const bool has_prev = (stf & 1) != 0, first = (stf & 2) != 0;
+    const int NP = md.NP;
+    const int S = 2 * NP + 5 + (XT ? op.nshape : 0);
+    double* s1 = chp->run_final + (size_t)bi_next * S;          // end state of the chunk just left ...
+    for (int i = tid; i < NP; i += MOSHII_TPB) { s1[i] = cx.pose[i]; s1[NP + i] = cx.pose_prev[i]; }
+    if (tid < 3) s1[2 * NP + tid] = cx.trans[tid];
+    if (tid == 3) s1[2 * NP + 3] = has_prev ? 1.0 : 0.0;
+    if (tid == 4) s1[2 * NP + 4] = first ? 1.0 : 0.0;
+    if constexpr (XT) for (int e = tid; e < op.nshape; e += MOSHII_TPB) s1[2 * NP + 5 + e] = cx.pose[NP + e];
+    if (chp->baton != nullptr) {
+        // Did a chain of this round start at the chunk being entered?  Its start state came from rows this chain has
+        // just replaced, so it is told to stop and this chain goes on in its place once it has (it notices within one
+        // frame).  Should it not stop within the patience below (it is not resident yet: more chains than CUs), this
+        // chain ends here instead and the next round continues it -- what every chain did before there was a baton.
+        if (tid == 0) {
+            int* st = chp->baton + 2 * (chp->chunk0 + 1 + bi_next);
+            double go = 1.0;
+            if (chp->fuse_flags != nullptr) {   // (first launch) has the chain of the chunk just left decided whether it carries on?
+                int* vd = chp->fuse_flags + 3 * (chp->chunk0 + bi_next) + 2;
+                int spins = 0;
+                while (__hip_atomic_load(vd, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 1) {
+                    __builtin_amdgcn_s_sleep(64);
+                    if (++spins > 20000) { go = 0.0; break; }
+                }
+            }
+            if (go != 0.0 && __hip_atomic_load(st, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 1) {
+                __hip_atomic_store(st + 1, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+                int spins = 0;
+                while (__hip_atomic_load(st, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 2) {
+                    __builtin_amdgcn_s_sleep(64);
+                    if (++spins > 20000) { go = 0.0; break; }   // (~2 us per look: some tens of milliseconds)
+                }
+            }
+            if (go != 0.0 && chp->fuse_flags != nullptr) {   // ... and has that chunk's own pass-1 chain written its last row?
+                int* od = chp->fuse_flags + 3 * (chp->chunk0 + 1 + bi_next) + 1;
+                int spins = 0;
+                while (__hip_atomic_load(od, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 1) {
+                    __builtin_amdgcn_s_sleep(64);
+                    if (++spins > 20000) { go = 0.0; break; }
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // the rows that chain stored are compared against below
+            cx.scal[S_BATON] = go;
+        }
+        __syncthreads();
+        if (cx.scal[S_BATON] == 0.0) { if (tid == 0 && chp->frames_done) *chp->frames_done = t; return 0; }
+    }
+    double* s2 = chp->run_entry + (size_t)(bi_next + 1) * S;    // ... is the state the next chunk is entered with
+    for (int i = tid; i < NP; i += MOSHII_TPB) { s2[i] = cx.pose[i]; s2[NP + i] = cx.pose_prev[i]; }
+    if (tid < 3) s2[2 * NP + tid] = cx.trans[tid];
+    if (tid == 3) s2[2 * NP + 3] = has_prev ? 1.0 : 0.0;
+    if (tid == 4) s2[2 * NP + 4] = first ? 1.0 : 0.0;
+    if constexpr (XT) for (int e = tid; e < op.nshape; e += MOSHII_TPB) s2[2 * NP + 5 + e] = cx.pose[NP + e];
+    return 1;
+}
+
+// Has an upstream chain of this round asked for this chain's territory (ChainDev::baton)?  Then the chain stops here (returns 1).  The
+// rows of the chunk this chain is in now switch from its own to older ones at frame t -- in the middle of a chunk, where no hand-off
+// check looks -- so the chunk's entry state is spoiled (an impossible flag value): unless the upstream chain sweeps it (it rewrites
+// the entry state when it gets there), the next verification fails it and it is re-solved from its predecessor's end state, which
+// this chain has just left behind.
+template <bool XT>
+__device__ __noinline__ int territory_request_fn(const ChainDev* chp_, int t_, int bi_next_) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const KernelCtx* kc = reinterpret_cast<const KernelCtx*>(lds);
+    MOSHII_CTX_FROM_KARGS(kc)
+    double* scal = lds + ly.o_scal;
+    const int tid = threadIdx.x;
+    const ChainDev* chp = uniform_ptr(chp_);
+    const int t = __builtin_amdgcn_readfirstlane(t_), bi_next = __builtin_amdgcn_readfirstlane(bi_next_);
+    const int NP = md.NP;
+    // (a slot of its own: S_BATON is written by thread 0, possibly before the others have read here)
+    if (tid == 0) scal[S_ABORT] = (double)__hip_atomic_load(&chp->baton[2 * chp->chunk0 + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (scal[S_ABORT] != 0.0) {
+        if (tid == 0) {
+            const int S = 2 * NP + 5 + (XT ? op.nshape : 0);
+            chp->run_entry[(size_t)bi_next * S + 2 * NP + 3] = MOSHII_MARK_ENTRY_SPOILED;
+            // ... and whoever re-solves this chunk starts by reproducing THIS chain's rows: it must not take that for
+            // having re-joined before it is past frame t
+            int* mark = chp->abort_at + chp->chunk0 + bi_next;
+            if (*mark < chp->bnd_off + t) *mark = chp->bnd_off + t;
+            if (chp->frames_done) *chp->frames_done = -t - 1;
+        }
+        return 1;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // One solver phase = one ch.minimize(method='dogleg') call over x = [trans, pose[ids]]
 // (oracle/stageii_oracle.py:minimize_dogleg), written as a single loop around ONE forward evaluation and
 // ONE normal-equation assembly so that each is instantiated once in the kernel.
@@ -2801,67 +3272,32 @@ __device__ __noinline__ void rigid_init_serial(const Ctx& cx, const FrameParams&
 // ------------------------------------------------------------------------------------------------
 // XT: the unknowns are x = [trans, pose[ids], shape coefficients (nshp of them, Step 2 only)]; the shape block is stored
 // behind the pose variables (cx.pose[NP ..]), so a shape column q has colpid[q] = NP + e and moves with the same code.
+// step2: the free set is Step 2's (OptsDev::step2; else Step 1's), nids pose ids (+ nshp shape coefficients) of it.
 template <int NBLK, bool XT, bool COOP>
-__device__ Sse run_phase(const Ctx& cx, const ChainLayout& ly, const ModelDev& md, const AttachDev& at, const PriorDev& pr,
-                         const OptsDev& op, const FrameParams& fp, const uint8_t* visrow, MOSHII_GP(const int) ids, int nids, int nshp,
+__device__ Sse run_phase(const BodyCtx& cx, const FrameParams& fp,
+                         const uint8_t* visrow, bool step2, int nids, int nshp,
                          double* qs, double e3,
                          bool rigid, bool eval_only, bool reuse, Sse& carried, bool& at_pose, int& fwd_set, int set_id, int& vc_key,
                          int& tab_key, int& n_iter, int& n_fev, int& fail, const CoopCtx& co) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
     const int tid = threadIdx.x;
     const int ncp = 3 + nids;
     const int n = ncp + (XT ? nshp : 0);
-    const int NPX = XT ? ly.NPX : md.NP;
-    // column tables + needed-joint lists of this free set; they stay in LDS until a solve with another set replaces them
-    // (body-only Stage-II uses one set throughout: built once per chain)
-    if (!eval_only && tab_key != set_id) {
+    // what the iteration loop needs of the descriptors, as named scalars read here, once per phase (body_args; the LDS offsets of the vectors
+    // the body holds anyway come from their pointers)
+    const BodyArgs ka = body_args(reinterpret_cast<const KernelCtx*>(lds));
+    const int NPX = XT ? ka->ly.NPX : ka->md.NP;
+    const int i_ksum = ka->ly.i_ksum, o_vconst = ka->ly.o_vconst, o_big = ka->ly.o_big, maxiter = ka->op.maxiter;
+    const int o_pose = (int)(cx.pose - lds), o_pose_t = (int)(cx.pose_t - lds), o_trans_t = (int)(cx.trans_t - lds), o_g = (int)(cx.g - lds);
+    if (!eval_only && tab_key != set_id) {   // the column tables + needed-joint lists in LDS are another free set's (or nobody's yet)
         tab_key = set_id;
-        for (int i = tid; i < md.NP; i += MOSHII_TPB) cx.colq[i] = -1;
-        __syncthreads();
-        for (int q = tid; q < n; q += MOSHII_TPB) {
-            const int pid = (q < 3) ? -1 : ((q < ncp) ? ids[q - 3] : md.NP + (q - ncp));
-            cx.colpid[q] = pid;
-            cx.colprior[q] = (pid >= 0 && pid < md.NP) ? cx.pid2prior[pid] : -1;
-            if (pid >= 0 && pid < md.NP) cx.colq[pid] = q;
-        }
-        if (tid == 0) {
-            for (int k = 0; k < md.K; ++k) cx.jointslot[k] = -1;
-            for (int i = 0; i < nids; ++i) {
-                const int pid = ids[i];
-                if (pid < md.body_dof) cx.jointslot[pid / 3] = 0;
-                else for (int k = md.body_dof / 3; k < md.K; ++k) cx.jointslot[k] = 0;
-            }
-            int c = 0;
-            for (int k = 0; k < md.K; ++k) if (cx.jointslot[k] == 0) { cx.jointslot[k] = c; cx.kfree[c] = k; ++c; }
-            cx.scal[S_TMP0] = (double)c;
-            int nh = 0;   // ids are sorted, so the hand-PCA coefficients (pid >= body_dof) are the trailing columns
-            for (int i = 0; i < nids; ++i) nh += (ids[i] >= md.body_dof) ? 1 : 0;
-            cx.scal[S_TMP2] = (double)nh;
-            // joints whose rotation moves during this solve (their pose correctives are re-summed at every evaluation)
-            // and the rest (summed once into cx.vconst); the root has no correctives
-            int ns = 0, nc = 0;
-            for (int k = 1; k < md.K; ++k) { if (cx.jointslot[k] >= 0) cx.ksum[ns++] = k; else cx.kconst[nc++] = k; }
-            cx.scal[S_TMP3] = (double)ns;
-        }
-        __syncthreads();
+        column_tables_fn<XT>(step2 ? 1 : 0);
     }
     const int nkf = (int)cx.scal[S_TMP0], nfree_hand = (int)cx.scal[S_TMP2];
     const int nks = (int)cx.scal[S_TMP3];   // (eval-only phases reuse the lists of the solve that preceded them)
-    const int nkc = md.K - 1 - nks;
-    if (vc_key != set_id) {
-        // cx.vconst = v_shaped + correctives of the joints that stay fixed in this solve, at the current pose.  It stays
-        // valid until a solve with a different free set runs (body-only Stage-II: computed once per chain).
-        for (int d = tid; d < md.P; d += MOSHII_TPB) cx.fullpose[d] = fullpose_entry(md, cx.pose, d);
-        __syncthreads();
-        if (tid < md.K) {
-            double R[9];
-            rodrigues_R(&cx.fullpose[3 * tid], R);
-#pragma unroll
-            for (int e = 0; e < 9; ++e) cx.feat[tid * 9 + e] = R[e] - ((e == 0 || e == 4 || e == 8) ? 1.0 : 0.0);
-        }
-        __syncthreads();
-        if constexpr (COOP) posedirs_partial_range(cx, at, cx.kconst, nkc, at.vsh, cx.vconst, 3 * co.mlo, 3 * co.mhi);
-        else posedirs_partial(cx, at, cx.kconst, nkc, at.vsh, cx.vconst);
-        __syncthreads();
+    const int nkc = ka->md.K - 1 - nks;
+    if (vc_key != set_id) {   // cx.vconst was summed for another free set's fixed joints
+        vconst_fn<COOP>(nkc);
         vc_key = set_id;
     }
     AReg<NBLK> A;
@@ -2869,7 +3305,6 @@ __device__ Sse run_phase(const Ctx& cx, const ChainLayout& ly, const ModelDev& m
     // the phase's parameters go to the context block at the head of the LDS, where eval_forward_fn / assemble_fn pick them up
     // (as a by-value argument they travelled through the stack in scratch memory at every call)
     if (tid == 0) {
-        extern __shared__ __attribute__((aligned(16))) double lds[];
         static_assert(sizeof(FrameParams) <= sizeof(KernelCtx::fp_raw), "KernelCtx::fp_raw too small");
         *reinterpret_cast<FrameParams*>(reinterpret_cast<KernelCtx*>(lds)->fp_raw) = fp;
     }
@@ -2877,7 +3312,7 @@ __device__ Sse run_phase(const Ctx& cx, const ChainLayout& ly, const ModelDev& m
     if (tid < 3) cx.trans_t[tid] = cx.trans[tid];
     __syncthreads();
     Sse last;
-    double sse = 0.0, delta = op.delta0, norm_sd = 0.0, norm_gn = 0.0, step = 0.0, p2 = 0.0, gd = 0.0;
+    double sse = 0.0, delta = ka->op.delta0, norm_sd = 0.0, norm_gn = 0.0, step = 0.0, p2 = 0.0, gd = 0.0;
     double dAd = 0.0, dl_dd = 0.0, dl_gs = 0.0, dl_ds = 0.0;   // d^T A d of the current step; the dogleg leg's sums of the current solve
     bool init = true, done = false, have_gn = false;
     int iteration = 0;
@@ -2891,38 +3326,14 @@ __device__ Sse run_phase(const Ctx& cx, const ChainLayout& ly, const ModelDev& m
     while (true) {
         int tid = threadIdx.x; MOSHII_OPAQUE(tid);
         if (skip_eval) { last = carried; skip_eval = false; }
-        else { PROF_T(_te); last = eval_forward_fn<XT, COOP>(visrow, ly.o_pose_t, ly.o_trans_t, ly.i_ksum, nks, ly.o_vconst, light); PROF_ACC(15, _te); }
+        else { PROF_T(_te); last = eval_forward_fn<XT, COOP>(visrow, o_pose_t, o_trans_t, i_ksum, nks, o_vconst, light); PROF_ACC(15, _te); }
         if constexpr (COOP) { if (cx.scal[S_COOP_FAIL] != 0.0) break; }   // the group is broken: unwind (the host reports the launch as failed)
         if (!(last.total == last.total)) { fail = 1; break; }   // a NaN objective: no comparison below would ever end the loop
         light = 0;
         at_pose = true;   // cleared below when a trial point is rejected
         fwd_set = set_id;
-        if (rigid) {   // rigid_transformations.py:72-83 on the markers just simulated
-            if constexpr (COOP) {   // every rank needs all the simulated markers: gather the ranks' rows (its own stay as they are)
-                const unsigned seq = coop_begin(cx);
-                auto gather = [&](auto l2) {   // (l2: the access scope, see coop_st_l2)
-                    constexpr bool L2 = decltype(l2)::value;
-                    auto* mine = coop_slot(co, seq, co.rank);
-                    for (int i = 3 * co.mlo + tid; i < 3 * co.mhi; i += MOSHII_TPB) coop_st64<L2>(mine + i, f64_bits(cx.msim[i]));
-                    if (tid == 0) coop_st64<L2>(mine + 3 * at.M, f64_bits((double)co.mlo));   // (where this rank's range starts)
-                    if (coop_publish_wait<L2>(co, cx, seq)) {
-                        const int M3 = 3 * at.M;
-                        for (int i = tid; i < M3; i += MOSHII_TPB) {
-                            // owner of marker i / 3: the rank whose range holds it (ranges are contiguous and ascending: count the boundaries passed)
-                            int r = 0;
-                            for (int q = 1; q < co.G; ++q) r += (i >= 3 * (int)bits_f64(coop_ld64<L2>(coop_slot(co, seq, q) + 3 * at.M))) ? 1 : 0;
-                            if (r != co.rank) cx.msim[i] = bits_f64(coop_ld64<L2>(coop_slot(co, seq, r) + i));
-                        }
-                    }
-                };
-                gather(std::false_type());
-                coop_end(cx, seq);
-            }
-            if (tid == 0) rigid_init_serial(cx, fp, visrow, at.M);
-            __syncthreads();
-            for (int i = tid; i < NPX; i += MOSHII_TPB) cx.pose_t[i] = cx.pose[i];
-            if (tid < 3) cx.trans_t[tid] = cx.trans[tid];
-            __syncthreads();
+        if (rigid) {   // the Procrustes init on the markers just simulated; the new point becomes the trial point
+            rigid_init_fn<XT, COOP>(visrow);
             rigid = false;
             continue;
         }
@@ -2950,7 +3361,7 @@ __device__ Sse run_phase(const Ctx& cx, const ChainLayout& ly, const ModelDev& m
         PROF_ACC(23, _t1);
         double pp = 0.0, gg = 0.0, gAg = 0.0;
         if (do_assemble) {
-            { PROF_T(_ta); A = APass<NBLK, MOSHII_ASM_RET_VEC(NBLK)>::unpack(assemble_fn<NBLK, XT, COOP>(ly.o_pose, n, ncp, nkf, nfree_hand, qs)); PROF_ACC(16, _ta); }
+            { PROF_T(_ta); A = APass<NBLK, MOSHII_ASM_RET_VEC(NBLK)>::unpack(assemble_fn<NBLK, XT, COOP>(o_pose, n, ncp, nkf, nfree_hand, qs)); PROF_ACC(16, _ta); }
             if constexpr (COOP) { if (cx.scal[S_COOP_FAIL] != 0.0) break; }
             PROF_T(_t2);
             // the gradient's maximum, |p|^2 at the accepted point, |g|^2 and g^T A g in ONE block reduction
@@ -2975,7 +3386,7 @@ __device__ Sse run_phase(const Ctx& cx, const ChainLayout& ly, const ModelDev& m
             if (delta <= 1e-15 * sqrt(pnorm2)) done = true;
         }
         if (init || improved) {
-            if (!init && iteration >= op.maxiter) done = true;
+            if (!init && iteration >= maxiter) done = true;
             if (done) break;
             // start_iteration: d_sd = |g|^2 / |J g|^2 g, with |J g|^2 = g^T A g
             ++iteration;
@@ -3000,8 +3411,8 @@ __device__ Sse run_phase(const Ctx& cx, const ChainLayout& ly, const ModelDev& m
                 constexpr bool BIG = XT && NBLK > 8;
                 bool solved;
                 PROF_T(_ts);
-                if constexpr (BIG) solved = ldl_big<NBLK>(A, qs + (size_t)6 * md.K * op.nshape, cx.big, cx.g, cx.dgn, cx.y, n);
-                else solved = ldl_solve<NBLK>(A, ly.o_big, ly.o_g, ly.o_dgn, ly.o_y, n);
+                if constexpr (BIG) solved = ldl_big<NBLK>(A, qs + (size_t)6 * ka->md.K * ka->op.nshape, lds + o_big, cx.g, cx.dgn, cx.y, n);
+                else solved = ldl_solve<NBLK>(A, o_big, o_g, o_g + 2 * 16 * NBLK, o_g + 4 * 16 * NBLK, n);   // (g, dgn, y: BodyCtx)
                 PROF_ACC(17, _ts);
                 PROF_ACC(26, _t4);   // (includes the solve: subtract slot 17)
                 if (!solved) {
@@ -3071,8 +3482,8 @@ __device__ Sse run_phase(const Ctx& cx, const ChainLayout& ly, const ModelDev& m
 //           write and sends its verdict to the other ranks at the top of every frame; the carry-on protocol of pass 1 (fuse_F) is the
 //           plain chains'.  Rank 0 writes the per-frame rows, every rank its own simulated markers.
 template <int NBLK, int MINW, bool XT, bool COOP = false>
-__global__ __launch_bounds__(MOSHII_TPB, MINW) void k_chain_solve(const ChainDev* __restrict__ chains, ModelDev md, PriorDev pr,
-                                                             OptsDev op, ChainLayout ly, int n_chains) {
+__global__ __launch_bounds__(MOSHII_TPB, MINW) void k_chain_solve(const ChainDev* __restrict__ chains, ModelDev a_md, PriorDev a_pr,
+                                                             OptsDev a_op, ChainLayout a_ly, int n_chains) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int tid = threadIdx.x;
     int chain_id = blockIdx.x;
@@ -3091,10 +3502,10 @@ __global__ __launch_bounds__(MOSHII_TPB, MINW) void k_chain_solve(const ChainDev
     const bool lead = !COOP || co.rank == 0;   // writes the rows every rank holds alike
     const ChainDev* chp = chains + chain_id;   // fields are (re)loaded where used: keeps SGPR pressure down
     const AttachDev at = *chp->att;
-    const Ctx cx = make_ctx(lds, ly);
+    const BodyCtx cx = make_body_ctx<NBLK>(lds, a_ly);
     if (tid == 0) {   // the descriptors for the separately compiled phases (eval_forward_fn / assemble_fn)
         KernelCtx* kc = reinterpret_cast<KernelCtx*>(lds);
-        kc->ly = ly; kc->md = md; kc->pr = pr; kc->op = op; kc->at = at;
+        kc->ly = a_ly; kc->md = a_md; kc->pr = a_pr; kc->op = a_op; kc->at = at;
 #if defined(__HIP_DEVICE_COMPILE__)
         kc->kargs = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
 #if !defined(MOSHII_NO_KARGS)
@@ -3102,7 +3513,7 @@ __global__ __launch_bounds__(MOSHII_TPB, MINW) void k_chain_solve(const ChainDev
             // (The parameter list as that one struct -- the same by construction -- does not compile: "Illegal instruction detected: Operand
             //  has incorrect register class" in one of the instantiations with hipcc 7.2.)  First, last and two middle fields against the arguments:
             const KArgsPtr kk = (KArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
-            if (kk->chains != chains || kk->n_chains != n_chains || kk->ly.total_doubles != ly.total_doubles || kk->md.V != md.V || kk->op.maxiter != op.maxiter)
+            if (kk->chains != chains || kk->n_chains != n_chains || kk->ly.total_doubles != a_ly.total_doubles || kk->md.V != a_md.V || kk->op.maxiter != a_op.maxiter)
                 __builtin_trap();   // (the launch fails: moshii_chain_solve reports the HIP error)
         }
 #endif
@@ -3110,9 +3521,10 @@ __global__ __launch_bounds__(MOSHII_TPB, MINW) void k_chain_solve(const ChainDev
         if constexpr (COOP) { kc->co = co; cx.scal[S_COOP_SEQ] = 0.0; cx.scal[S_COOP_FAIL] = 0.0; }
     }
 
-    const int NP = md.NP, M = at.M, F = chp->F, skip = chp->skip;
+    const int NP = a_md.NP, M = at.M, F = chp->F, skip = chp->skip;
     bool has_prev, first;
     {
+        const Ctx cs = make_ctx(lds, a_ly);   // (the chain's set-up alone writes these parts of the LDS from the body)
         const double* is = chp->init_state;
         const double* ip = chp->init_pose;
         const double* iv = chp->init_prev;
@@ -3121,26 +3533,26 @@ __global__ __launch_bounds__(MOSHII_TPB, MINW) void k_chain_solve(const ChainDev
             cx.pose[i] = is ? is[i] : (ip ? ip[i] : 0.0);
             cx.pose_prev[i] = is ? is[NP + i] : (iv ? iv[i] : 0.0);
             cx.vtarget[i] = 0.0;
-            cx.pid2prior[i] = -1;
+            cs.pid2prior[i] = -1;
         }
         if (tid < 3) cx.trans[tid] = is ? is[2 * NP + tid] : (it ? it[tid] : 0.0);
         if constexpr (XT) {
             const double* ish = chp->init_shape;
             // (chunk hand-off states carry the coefficients behind the flags: [pose][pose_prev][trans][has_prev][first][shape])
-            for (int e = tid; e < op.nshape; e += MOSHII_TPB) { cx.pose[NP + e] = is ? is[2 * NP + 5 + e] : (ish ? ish[e] : 0.0); cx.shp0[e] = 0.0; }
+            for (int e = tid; e < a_op.nshape; e += MOSHII_TPB) { cx.pose[NP + e] = is ? is[2 * NP + 5 + e] : (ish ? ish[e] : 0.0); cs.shp0[e] = 0.0; }
         }
         has_prev = is ? (is[2 * NP + 3] != 0.0) : (iv != nullptr);
         first = is ? (is[2 * NP + 4] != 0.0) : (chp->first != 0);
+        if (tid == 0) cx.scal[S_PRIOR_REF] = 0.0;   // no prior reference point yet (eval_forward)
+        // the prior's partial-sum slices and the slack behind them are read past a wave's own entries (times 0) before the neighbouring
+        // wave has necessarily written them on the first evaluation: keep every word finite from the start (stale LDS bits could be NaN)
+        for (int i = tid; i < 8 * a_pr.npose + 16; i += MOSHII_TPB) cs.ell[i] = 0.0;
+        if (tid < a_md.K) cs.anc[tid] = a_md.anc[tid];
+        for (int i = tid; i < 3 * a_md.K; i += MOSHII_TPB) cs.Jl[i] = a_md.J[i];   // regressed joints: read in every phase, keep them in LDS
+        __syncthreads();
+        for (int b = tid; b < a_op.nbody; b += MOSHII_TPB) cs.pid2prior[a_op.body[b]] = b;
+        __syncthreads();
     }
-    if (tid == 0) cx.scal[S_PRIOR_REF] = 0.0;   // no prior reference point yet (eval_forward)
-    // the prior's partial-sum slices and the slack behind them are read past a wave's own entries (times 0) before the neighbouring
-    // wave has necessarily written them on the first evaluation: keep every word finite from the start (stale LDS bits could be NaN)
-    for (int i = tid; i < 8 * pr.npose + 16; i += MOSHII_TPB) cx.ell[i] = 0.0;
-    if (tid < md.K) cx.anc[tid] = md.anc[tid];
-    for (int i = tid; i < 3 * md.K; i += MOSHII_TPB) cx.Jl[i] = md.J[i];   // regressed joints: read in every phase, keep them in LDS
-    __syncthreads();
-    for (int b = tid; b < op.nbody; b += MOSHII_TPB) cx.pid2prior[op.body[b]] = b;
-    __syncthreads();
     int vc_key = 0, tab_key = 0;   // which free set cx.vconst / the column tables were built for (0: none yet)
     int rejoin_run = 0;            // consecutive frames that reproduced the stored trajectory (repair chains)
     int bi_next = 0;               // next chunk boundary of a run-through repair chain
@@ -3155,6 +3567,13 @@ __global__ __launch_bounds__(MOSHII_TPB, MINW) void k_chain_solve(const ChainDev
     bool tail_cut = false;
     for (int t = 0; t <= F; ++t) {
         PROF_T(_tf);
+        // From here on the descriptors are read where they are used, from the argument segment (body_args): the by-value parameters are
+        // loaded at the kernel's entry in tuples of up to 16 registers, every tuple the loop touched stayed live -- parked in vector lanes --
+        // across the whole frame loop and came back whole for one field of it.  (The parameters are a_md, a_pr, a_op, a_ly: the set-up's.)
+        const BodyArgs ka = body_args(reinterpret_cast<const KernelCtx*>(lds));
+        const auto& md = ka->md;
+        const auto& op = ka->op;
+        const auto& ly = ka->ly;
         if constexpr (!COOP && !XT) {   // (armed for body / finger solves only: moshii_sequence_solve runs extended solves without cooperative sweeps)
             // the tail of a pass-1 launch (ChainDev::tail_done): most of the other chunks are done and this one is far from it -- give the chunk up
             if (chp->tail_done != nullptr && chp->tail_can_cut != 0 && t < F && F - t > chp->tail_left) {
@@ -3186,59 +3605,8 @@ __global__ __launch_bounds__(MOSHII_TPB, MINW) void k_chain_solve(const ChainDev
             if (chp->baton != nullptr || chp->nb > 0 || chp->rejoin_tol > 0.0) {   // (descriptor constants: the same on every rank)
                 bool halt = false;
                 if (lead) {
-                    const int S = 2 * NP + 5;
-                    if (rejoin_run >= 2 && t < F) {   // the previous frame's verdict: pose and pose_prev both match, the stored rows (and final state) stand
-                        if (tid == 0 && chp->frames_done) *chp->frames_done = t;
-                        halt = true;
-                    }
-                    if (!halt && bi_next < chp->nb && t == chp->bnd[bi_next] - chp->bnd_off) {   // a chunk boundary (see the plain chain below)
-                        double* s1 = chp->run_final + (size_t)bi_next * S;
-                        for (int i = tid; i < NP; i += MOSHII_TPB) { s1[i] = cx.pose[i]; s1[NP + i] = cx.pose_prev[i]; }
-                        if (tid < 3) s1[2 * NP + tid] = cx.trans[tid];
-                        if (tid == 3) s1[2 * NP + 3] = has_prev ? 1.0 : 0.0;
-                        if (tid == 4) s1[2 * NP + 4] = first ? 1.0 : 0.0;
-                        if (chp->baton != nullptr) {
-                            if (tid == 0) {
-                                int* st = chp->baton + 2 * (chp->chunk0 + 1 + bi_next);
-                                double go = 1.0;
-                                if (__hip_atomic_load(st, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 1) {
-                                    __hip_atomic_store(st + 1, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-                                    int spins = 0;
-                                    while (__hip_atomic_load(st, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 2) {
-                                        __builtin_amdgcn_s_sleep(64);
-                                        if (++spins > 20000) { go = 0.0; break; }
-                                    }
-                                }
-                                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                                cx.scal[S_BATON] = go;
-                            }
-                            __syncthreads();
-                            if (cx.scal[S_BATON] == 0.0) { if (tid == 0 && chp->frames_done) *chp->frames_done = t; halt = true; }
-                            __syncthreads();
-                        }
-                        if (!halt) {
-                            double* s2 = chp->run_entry + (size_t)(bi_next + 1) * S;
-                            for (int i = tid; i < NP; i += MOSHII_TPB) { s2[i] = cx.pose[i]; s2[NP + i] = cx.pose_prev[i]; }
-                            if (tid < 3) s2[2 * NP + tid] = cx.trans[tid];
-                            if (tid == 3) s2[2 * NP + 3] = has_prev ? 1.0 : 0.0;
-                            if (tid == 4) s2[2 * NP + 4] = first ? 1.0 : 0.0;
-                            ++bi_next;
-                        }
-                    }
-                    if (!halt && chp->baton != nullptr && t < F) {   // has an upstream chain of this round asked for this chain's territory?
-                        if (tid == 0) cx.scal[S_ABORT] = (double)__hip_atomic_load(&chp->baton[2 * chp->chunk0 + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __syncthreads();
-                        if (cx.scal[S_ABORT] != 0.0) {
-                            if (tid == 0) {
-                                chp->run_entry[(size_t)bi_next * S + 2 * NP + 3] = MOSHII_MARK_ENTRY_SPOILED;
-                                int* mark = chp->abort_at + chp->chunk0 + bi_next;
-                                if (*mark < chp->bnd_off + t) *mark = chp->bnd_off + t;
-                                if (chp->frames_done) *chp->frames_done = -t - 1;
-                            }
-                            halt = true;
-                        }
-                        __syncthreads();
-                    }
+                    const int v = __builtin_amdgcn_readfirstlane(coop_lead_verdict_fn(chp, t, rejoin_run, bi_next, (has_prev ? 1 : 0) | (first ? 2 : 0)));
+                    halt = (v & 1) != 0; bi_next = v >> 1;
                 }
                 const unsigned seq = coop_begin(cx);
                 const double mine[1] = {halt ? 1.0 : 0.0};
@@ -3258,189 +3626,23 @@ __global__ __launch_bounds__(MOSHII_TPB, MINW) void k_chain_solve(const ChainDev
             if (tid == 4) so[2 * NP + 4] = first ? 1.0 : 0.0;
             if constexpr (XT) for (int e = tid; e < op.nshape; e += MOSHII_TPB) so[2 * NP + 5 + e] = cx.pose[NP + e];
         }
-        if (!COOP && chp->fuse_flags != nullptr) {
-            const int S = 2 * NP + 5 + (XT ? op.nshape : 0);
-            if (t == skip && chp->entry_state != nullptr) {   // the entry state is out: the left neighbour may compare with it
-                __syncthreads();
-                if (tid == 0) { __threadfence(); __hip_atomic_store(&chp->fuse_flags[3 * chp->fuse_c], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
-            }
-            if (chp->fuse_F == 0 && t == F) {                  // (a chain without a right neighbour: its rows are complete ...
-                __syncthreads();
-                if (tid == 0) {
-                    __threadfence();
-                    __hip_atomic_store(&chp->fuse_flags[3 * chp->fuse_c + 1], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-                    // ... and it never carries on: its verdict is final too.  The chain of the chunk before it waits for BOTH flags
-                    // before it takes this chunk over; without this store it waited out its whole patience and left the
-                    // last chunk of every sequence to a host round.)
-                    __hip_atomic_store(&chp->fuse_flags[3 * chp->fuse_c + 2], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-            if (chp->fuse_F > 0 && t == chp->fuse_F) {
-                // The end of this chain's own chunk (ChainDev::fuse_F): its end state ...
-                double* sf = chp->run_final - S;
-                for (int i = tid; i < NP; i += MOSHII_TPB) { sf[i] = cx.pose[i]; sf[NP + i] = cx.pose_prev[i]; }
-                if (tid < 3) sf[2 * NP + tid] = cx.trans[tid];
-                if (tid == 3) sf[2 * NP + 3] = has_prev ? 1.0 : 0.0;
-                if (tid == 4) sf[2 * NP + 4] = first ? 1.0 : 0.0;
-                if constexpr (XT) for (int e = tid; e < op.nshape; e += MOSHII_TPB) sf[2 * NP + 5 + e] = cx.pose[NP + e];
-                __syncthreads();
-                if (tid == 0) { __threadfence(); __hip_atomic_store(&chp->fuse_flags[3 * chp->fuse_c + 1], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }   // this chunk's rows are complete
-                // ... against the entry state the next chunk's chain recorded a chunk ago (it only has to be waited for when the
-                // chunks are not all resident -- then this chain gives up quickly and the host's rounds do the rest)
-                bool carry = false;
-                auto state_dev = [&](const double* en) {   // max |this chain's state - en| (flags must be equal; NaN counts as a miss)
-                    double dv = 0.0, nn = 0.0;
-                    for (int i = tid; i < NP; i += MOSHII_TPB) { dv = fmax(dv, fmax(fabs(cx.pose[i] - en[i]), fabs(cx.pose_prev[i] - en[NP + i]))); nn += en[i] + en[NP + i]; }
-                    if (tid < 3) dv = fmax(dv, fabs(cx.trans[tid] - en[2 * NP + tid]));
-                    if (tid == 3 && (has_prev ? 1.0 : 0.0) != en[2 * NP + 3]) dv = MOSHII_HANDOFF_MISMATCH;
-                    if (tid == 4 && (first ? 1.0 : 0.0) != en[2 * NP + 4]) dv = MOSHII_HANDOFF_MISMATCH;
-                    if constexpr (XT) for (int e = tid; e < op.nshape; e += MOSHII_TPB) dv = fmax(dv, fabs(cx.pose[NP + e] - en[2 * NP + 5 + e]));
-                    if (!(nn == nn)) dv = MOSHII_HANDOFF_MISMATCH;
-                    return block_max(dv, cx.red);
-                };
-                auto wait_flag = [&](int* fl, int patience) {   // thread 0 waits (bounded) for *fl == 1; every thread gets the outcome
-                    if (tid == 0) {
-                        double go = 1.0;
-                        int spins = 0;
-                        while (__hip_atomic_load(fl, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 1) {
-                            __builtin_amdgcn_s_sleep(64);
-                            if (++spins > patience) { go = 0.0; break; }
-                        }
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                        cx.scal[S_BATON] = go;
-                    }
-                    __syncthreads();
-                    const bool ok_ = cx.scal[S_BATON] != 0.0;
-                    __syncthreads();
-                    return ok_;
-                };
-                if (chp->fuse_has_next && wait_flag(chp->fuse_flags + 3 * (chp->fuse_c + 1), 2000)) {
-                    const double dv = state_dev(chp->run_entry);
-                    carry = !(dv <= chp->fuse_tol);
-                    // A gross miss (another basin) is only this chain's to repair if its OWN chunk stands on firm ground: if the hand-off
-                    // INTO this chunk missed grossly too, this chain's state is the suspect one and the sweep that repairs this chunk
-                    // will deal with the next boundary when it gets there (the rule the host applies to its repair rounds).  The left
-                    // neighbour finishes at about the same time; if it has not, the chain goes ahead.
-                    if (carry && dv > 1e-6 && chp->fuse_has_prev && wait_flag(chp->fuse_flags + 3 * (chp->fuse_c - 1) + 1, 150)) {
-                        const double* lf = chp->run_final - 2 * S;   // end state of the left neighbour
-                        const double* oe = chp->run_entry - S;       // the entry state this chain recorded
-                        double dl = 0.0;
-                        for (int i = tid; i < 2 * NP + 3; i += MOSHII_TPB) dl = fmax(dl, fabs(lf[i] - oe[i]));
-                        dl = block_max(dl, cx.red);
-                        if (!(dl <= 1e-6)) carry = false;
-                    }
-                }
-                // The verdict (a chain will start at the next chunk, or not) is in place before it is declared final: a sweep
-                // arriving at the next boundary waits for that declaration before it looks.
-                if (carry && tid == 0) __hip_atomic_store(&chp->baton[2 * chp->chunk0], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-                __syncthreads();
-                if (tid == 0) { __threadfence(); __hip_atomic_store(&chp->fuse_flags[3 * chp->fuse_c + 2], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
-                if (!carry) { if (tid == 0 && chp->frames_done) *chp->frames_done = t; break; }
-                // Carry on as the repair chain of the next chunk -- once that chunk's own chain has written its last row (from here on
-                // its rows are compared against and replaced), unless an upstream sweep asks for this territory meanwhile.
-                if (tid == 0) {
-                    int* fl = chp->fuse_flags + 3 * (chp->fuse_c + 1) + 1;
-                    double go = 1.0;
-                    int spins = 0;
-                    // (... AND has given its own verdict: until then it may still read the entry state it recorded -- the slot written
-                    //  below -- for its "is my own chunk on firm ground" test; overwriting it earlier made that test compare this
-                    //  chain's end state with itself)
-                    while (__hip_atomic_load(fl, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 1 ||
-                           __hip_atomic_load(fl + 1, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 1) {
-                        if (__hip_atomic_load(&chp->baton[2 * chp->chunk0 + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) { go = 0.0; break; }
-                        __builtin_amdgcn_s_sleep(64);
-                        if (++spins > 20000) { go = 0.0; break; }
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                    if (go != 0.0 && chp->fuse_count != nullptr) atomicAdd(chp->fuse_count, 1);
-                    cx.scal[S_BATON] = go;
-                }
-                __syncthreads();
-                if (cx.scal[S_BATON] == 0.0) { if (tid == 0 && chp->frames_done) *chp->frames_done = t; break; }
-                double* s2 = chp->run_entry;   // the next chunk is entered with this state
-                for (int i = tid; i < NP; i += MOSHII_TPB) { s2[i] = cx.pose[i]; s2[NP + i] = cx.pose_prev[i]; }
-                if (tid < 3) s2[2 * NP + tid] = cx.trans[tid];
-                if (tid == 3) s2[2 * NP + 3] = has_prev ? 1.0 : 0.0;
-                if (tid == 4) s2[2 * NP + 4] = first ? 1.0 : 0.0;
-                if constexpr (XT) for (int e = tid; e < op.nshape; e += MOSHII_TPB) s2[2 * NP + 5 + e] = cx.pose[NP + e];
-                fuse_on = true;
+        // the chunk protocol of plain chains, at the frames where it has something to do (out of line: carry_on_fn, chunk_boundary_fn, territory_request_fn)
+        if constexpr (!COOP) {
+            if (chp->fuse_flags != nullptr && (t == skip || t == chp->fuse_F || (t == F && chp->fuse_F == 0))) {
+                const int v = __builtin_amdgcn_readfirstlane(carry_on_fn<XT>(chp, t, (has_prev ? 1 : 0) | (first ? 2 : 0)));
+                if (v == 1) break;
+                if (v == 2) fuse_on = true;
             }
         }
         const bool sweeping = chp->fuse_F == 0 || fuse_on;   // (a pass-1 chain inside its own chunk is not a repair chain yet)
-        if (!COOP && bi_next < chp->nb && t == chp->bnd[bi_next] - chp->bnd_off) {   // a chunk boundary inside a run-through repair chain
-            const int S = 2 * NP + 5 + (XT ? op.nshape : 0);
-            double* s1 = chp->run_final + (size_t)bi_next * S;          // end state of the chunk just left ...
-            for (int i = tid; i < NP; i += MOSHII_TPB) { s1[i] = cx.pose[i]; s1[NP + i] = cx.pose_prev[i]; }
-            if (tid < 3) s1[2 * NP + tid] = cx.trans[tid];
-            if (tid == 3) s1[2 * NP + 3] = has_prev ? 1.0 : 0.0;
-            if (tid == 4) s1[2 * NP + 4] = first ? 1.0 : 0.0;
-            if constexpr (XT) for (int e = tid; e < op.nshape; e += MOSHII_TPB) s1[2 * NP + 5 + e] = cx.pose[NP + e];
-            if (chp->baton != nullptr) {
-                // Did a chain of this round start at the chunk being entered?  Its start state came from rows this chain has
-                // just replaced, so it is told to stop and this chain goes on in its place once it has (it notices within one
-                // frame).  Should it not stop within the patience below (it is not resident yet: more chains than CUs), this
-                // chain ends here instead and the next round continues it -- what every chain did before there was a baton.
-                if (tid == 0) {
-                    int* st = chp->baton + 2 * (chp->chunk0 + 1 + bi_next);
-                    double go = 1.0;
-                    if (chp->fuse_flags != nullptr) {   // (first launch) has the chain of the chunk just left decided whether it carries on?
-                        int* vd = chp->fuse_flags + 3 * (chp->chunk0 + bi_next) + 2;
-                        int spins = 0;
-                        while (__hip_atomic_load(vd, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 1) {
-                            __builtin_amdgcn_s_sleep(64);
-                            if (++spins > 20000) { go = 0.0; break; }
-                        }
-                    }
-                    if (go != 0.0 && __hip_atomic_load(st, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 1) {
-                        __hip_atomic_store(st + 1, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-                        int spins = 0;
-                        while (__hip_atomic_load(st, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 2) {
-                            __builtin_amdgcn_s_sleep(64);
-                            if (++spins > 20000) { go = 0.0; break; }   // (~2 us per look: some tens of milliseconds)
-                        }
-                    }
-                    if (go != 0.0 && chp->fuse_flags != nullptr) {   // ... and has that chunk's own pass-1 chain written its last row?
-                        int* od = chp->fuse_flags + 3 * (chp->chunk0 + 1 + bi_next) + 1;
-                        int spins = 0;
-                        while (__hip_atomic_load(od, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 1) {
-                            __builtin_amdgcn_s_sleep(64);
-                            if (++spins > 20000) { go = 0.0; break; }
-                        }
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // the rows that chain stored are compared against below
-                    cx.scal[S_BATON] = go;
-                }
-                __syncthreads();
-                if (cx.scal[S_BATON] == 0.0) { if (tid == 0 && chp->frames_done) *chp->frames_done = t; break; }
+        if constexpr (!COOP) {
+            const int stf = (has_prev ? 1 : 0) | (first ? 2 : 0);
+            if (bi_next < chp->nb && t == chp->bnd[bi_next] - chp->bnd_off) {   // a chunk boundary inside a run-through repair chain
+                if (__builtin_amdgcn_readfirstlane(chunk_boundary_fn<XT>(chp, t, bi_next, stf)) == 0) break;
+                ++bi_next;
             }
-            double* s2 = chp->run_entry + (size_t)(bi_next + 1) * S;    // ... is the state the next chunk is entered with
-            for (int i = tid; i < NP; i += MOSHII_TPB) { s2[i] = cx.pose[i]; s2[NP + i] = cx.pose_prev[i]; }
-            if (tid < 3) s2[2 * NP + tid] = cx.trans[tid];
-            if (tid == 3) s2[2 * NP + 3] = has_prev ? 1.0 : 0.0;
-            if (tid == 4) s2[2 * NP + 4] = first ? 1.0 : 0.0;
-            if constexpr (XT) for (int e = tid; e < op.nshape; e += MOSHII_TPB) s2[2 * NP + 5 + e] = cx.pose[NP + e];
-            ++bi_next;
-        }
-        if (!COOP && chp->baton != nullptr && sweeping && t < F) {
-            // Has an upstream chain of this round asked for this chain's territory (ChainDev::baton)?  Then stop here.  The rows
-            // of the chunk this chain is in now switch from its own to older ones at frame t -- in the middle of a chunk, where
-            // no hand-off check looks -- so the chunk's entry state is spoiled (an impossible flag value): unless the upstream
-            // chain sweeps it (it rewrites the entry state when it gets there), the next verification fails it and it is
-            // re-solved from its predecessor's end state, which this chain has just left behind.
-            // (a slot of its own: S_BATON above is written by thread 0, possibly before the others have read here)
-            if (tid == 0) cx.scal[S_ABORT] = (double)__hip_atomic_load(&chp->baton[2 * chp->chunk0 + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __syncthreads();
-            if (cx.scal[S_ABORT] != 0.0) {
-                if (tid == 0) {
-                    const int S = 2 * NP + 5 + (XT ? op.nshape : 0);
-                    chp->run_entry[(size_t)bi_next * S + 2 * NP + 3] = MOSHII_MARK_ENTRY_SPOILED;
-                    // ... and whoever re-solves this chunk starts by reproducing THIS chain's rows: it must not take that for
-                    // having re-joined before it is past frame t
-                    int* mark = chp->abort_at + chp->chunk0 + bi_next;
-                    if (*mark < chp->bnd_off + t) *mark = chp->bnd_off + t;
-                    if (chp->frames_done) *chp->frames_done = -t - 1;
-                }
-                break;
+            if (chp->baton != nullptr && sweeping && t < F) {
+                if (__builtin_amdgcn_readfirstlane(territory_request_fn<XT>(chp, t, bi_next)) != 0) break;
             }
         }
         if (t == F) break;
@@ -3490,7 +3692,8 @@ __global__ __launch_bounds__(MOSHII_TPB, MINW) void k_chain_solve(const ChainDev
             // "extrap_dmpl" (:693-697): dmpl_prev was refreshed at :658-659, so the term pulls towards the value the
             // coefficients have on entering this frame -- from the second solved frame on
             fp.has_stay = (!first && op.wt_shape_stay != 0.0) ? 1 : 0;
-            for (int e = tid; e < op.nshape; e += MOSHII_TPB) cx.shp0[e] = cx.pose[NP + e];
+            double* shp0 = lds + ly.o_shp0;
+            for (int e = tid; e < op.nshape; e += MOSHII_TPB) shp0[e] = cx.pose[NP + e];
         }
         fp.has_velo = has_prev ? 1 : 0;
         if (has_prev)   // :624-626  target = pose.r + (pose.r - pose_prev)
@@ -3519,7 +3722,7 @@ __global__ __launch_bounds__(MOSHII_TPB, MINW) void k_chain_solve(const ChainDev
             }
             const int terms = fp.use_fingers | (fp.use_face << 1) | (fp.use_shape << 2);   // the Step-2-only residual blocks
             const bool reuse = at_pose && prev_wt_pose == fp.wt_pose && prev_terms == terms;
-            fin = run_phase<NBLK, XT, COOP>(cx, ly, md, at, pr, op, fp, visrow, step2 ? op.step2 : op.step1, step2 ? op.n2 : op.n1,
+            fin = run_phase<NBLK, XT, COOP>(cx, fp, visrow, step2, step2 ? op.n2 : op.n1,
                                   (XT && step2) ? op.nshape : 0, XT ? chp->qscratch + (COOP ? (size_t)co.rank * chp->coop.qstride : 0) : nullptr,
                                   round ? op.e3_first : op.e3, /*rigid=*/kind == 0, /*eval_only=*/kind == 5, reuse, carried, at_pose, fwd_set,
                                   /*set_id=*/(kind >= 4 && !same_sets) ? 2 : 1, vc_key, tab_key, n_iter, n_fev, fail, co);

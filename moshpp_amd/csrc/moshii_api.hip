@@ -1348,6 +1348,11 @@ int prepare_launch(moshii_model_t m, moshii_prior_t prior, const moshii_solve_op
     int rc;
     if ((rc = check_opts(m, prior, o, &d))) return rc;
     if ((rc = choose_layout(m, d, Mmax, Nvmax, NWmax, n_workgroups, coop_g, cfg))) return rc;
+    // (the kernel body takes these distances for granted: a make_layout that no longer keeps them must not reach the device)
+#ifdef MOSHII_EMULATION   // test hook of the CPU build only: the layout as a make_layout that had grown a field between dsd and dgn would leave it
+    if (getenv("MOSHII_TEST_BREAK_LAYOUT")) { cfg->ly.o_dgn += 2; cfg->ly.o_ddl += 2; cfg->ly.o_y += 2; cfg->ly.o_red += 2; cfg->ly.o_scal += 2; }
+#endif
+    if (const char* why = chain_layout_fault(cfg->ly, cfg->nblk)) return fail(MOSHII_ERR_UNSUPPORTED, std::string("internal error: ") + why);
     return upload_ids(m, prior, o, stream, extra_bytes, cfg, ctl_off);
 }
 

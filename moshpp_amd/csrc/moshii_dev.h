@@ -208,6 +208,18 @@ struct ChainLayout {
     // tile sub-offsets inside big (in doubles)
     int t_Jh, t_Jrow, t_Lm, t_Trot, t_xjs, t_rest, t_tjs;
 };
+// The chain kernel's body (chain_solve.hip: BodyCtx) reaches the control vectors g, dsd, dgn, ddl, y, the reduction pad and the scalars
+// from ONE base with compile-time distances -- LDJ = 16 nblk doubles apart, then 16 and 16 -- and the column table colprior LDJ ints
+// behind colpid.  Null if `ly` has them for the `nblk`-block instantiation; else what is wrong (the host refuses the launch).
+inline const char* chain_layout_fault(const ChainLayout& ly, int nblk) {
+    const int LDJ = 16 * nblk;
+    if (nblk <= 0 || ly.LDJ != LDJ) return "chain layout: LDJ is not 16 register blocks";
+    if (ly.o_dsd - ly.o_g != LDJ || ly.o_dgn - ly.o_g != 2 * LDJ || ly.o_ddl - ly.o_g != 3 * LDJ || ly.o_y - ly.o_g != 4 * LDJ)
+        return "chain layout: the control vectors g, dsd, dgn, ddl, y are not LDJ doubles apart";
+    if (ly.o_red - ly.o_g != 5 * LDJ || ly.o_scal - ly.o_red != 16) return "chain layout: red / scal do not follow the control vectors";
+    if (ly.i_colprior - ly.i_colpid != LDJ) return "chain layout: colprior is not LDJ ints behind colpid";
+    return nullptr;
+}
 
 // Copy of the chain kernel's descriptors at the head of its dynamic LDS (ChainLayout offsets start behind it): the phases
 // of the solver that are compiled as functions of their own (chain_solve.hip) pick their context up from here instead of
